@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the deepFEPE weighted-8-point hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--scaling {weak,strong}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--scaling {weak,strong}] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -16,8 +16,13 @@ per-layer logits.  Inputs already live in HBM when the timed region starts.  The
 Data parallel over N ranks: every rank owns its shard of independent pairs (the pairs never interact), the only exchange
 is one all-reduce of the small loss vector per step (RCCL) where the step has a loss.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel against the HBM roofline,
-measured with HIP events on the launch stream) and `cpu_baseline` (the CPU oracle on a bounded sample of the same workload).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps and prints
+the line (`value`, `ms_per_step`, the accuracy of the last step's own outputs) -- nothing else.  `--full` adds every
+informational measurement behind it: `block_stats` (repeated 20-step blocks), `roofline` (dominant kernel against the HBM
+roofline, measured with HIP events on the launch stream), `cpu_baseline` (the CPU oracle on a bounded sample of the same
+workload), and for config 3 the variants of the step, the reference-API path, the whole model and the matcher.
+`--dump-outputs DIR` writes what the timed path computed in its last timed step (rank 0's pairs) as DIR/<name>.npy, float32
+or float64, at most 64 MB in all; the inputs are seeded, so two builds run with the same arguments compare output for output.
 """
 import argparse
 import importlib
@@ -67,7 +72,13 @@ def parse(argv=None):
     ap.add_argument("--npoints", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--outliers", type=float, default=None)
-    ap.add_argument("--blocks", type=int, default=10, help="informational: repeated 20-step blocks after the timed region (median, spread)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every informational measurement (blocks, roofline, CPU baseline, step variants, API path, whole model, "
+                         "matcher); a plain run only times the step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--blocks", type=int, default=10,
+                    help="informational (--full): repeated 20-step blocks after the timed region (median, spread)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-full-model", action="store_true", help="skip the secondary whole-DeepFNet measurement")
@@ -80,7 +91,42 @@ def parse(argv=None):
                     help="auto: a plain `python bench.py --gpus N` (no RANK in the environment) with N > 1 re-executes itself under "
                          "torch.distributed.run with N ranks; torchrun: do that even for N = 1 (exercises the launch path on a 1-GPU box); "
                          "none: never re-execute")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: array data in all, so that the files stay below 64 MB with their headers
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: tensor or list of per-layer tensors} as outdir/<name>.npy: float64 stays float64, every other dtype becomes
+    float32.  Over DUMP_BYTES in all, every array above 1 MB is cut to the same fraction of its elements, a fixed seeded sample of
+    flat indices (sorted), so that two runs with the same arguments write the same elements."""
+    import numpy as np
+
+    host = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        if isinstance(t, (list, tuple)):
+            t = torch.stack(list(t))
+        t = t.detach()
+        host[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().contiguous()
+    big_limit = 1 << 20
+    small = sum(t.numel() * t.element_size() for t in host.values() if t.numel() * t.element_size() <= big_limit)
+    big = sum(t.numel() * t.element_size() for t in host.values() if t.numel() * t.element_size() > big_limit)
+    frac = 1.0 if small + big <= DUMP_BYTES else (DUMP_BYTES - small) / big
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in host.items():
+        a = t.reshape(-1) if frac < 1.0 and t.numel() * t.element_size() > big_limit else t
+        if a is not t:
+            k = int(t.numel() * frac)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            a = a[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a.numpy())
+    log("outputs written to", outdir, "sampled" if frac < 1.0 else "whole", sorted(host))
 
 
 def capture_mode():
@@ -388,17 +434,20 @@ def main():
             g, = torch.autograd.grad(out["loss"], logits, grad_outputs=state["seed"])
             state["grad_logits"] = g           # d loss / d logits: what the estimator's backward / an optimizer consumes
             state["loss_vec"] = out["packed"]  # dist.pack_loss_sums layout (L+4 doubles): the ONLY data exchanged between ranks
+            state["out"] = dict(out, grad_logits=g)  # what a caller of the step receives (--dump-outputs)
             return out
     elif kind == "fit":
         def step_body():
             F, res, epi, _, _ = dfepe.ops.w8pt_forward(m, None, w0, True, W, H, 0.5, True, False)
             state["E"] = dfepe.ops.congruence(F, TK)
+            state["out"] = {"F_layers": F.unsqueeze(0), "residual": res, "epi": epi, "E": state["E"]}
             return {"F_layers": F.unsqueeze(0), "residual": res, "epi": epi}
     else:  # "pose": fit + E-from-F + cheirality-checked decomposition (the (1,1,0) projection is implied by the decomposition)
         def step_body():
             # E = (T K)^T F (T K) is formed inside; one launch when a cooperative workgroup serves the pair (small batches), else two
             F, res, epi, _, Rt, winner, counts = dfepe.ops.fit_pose(m, w0, scene["Ks"], W, H, 50.0, pre=TK)
             state["Rt"], state["winner"] = Rt, winner
+            state["out"] = {"F_layers": F.unsqueeze(0), "residual": res, "epi": epi, "Rt": Rt, "winner": winner, "counts": counts}
             return {"F_layers": F.unsqueeze(0), "Rt": Rt, "winner": winner, "counts": counts}
 
     # eager warm-up (also sizes the caching allocator), then optional graph capture of the whole step
@@ -485,10 +534,12 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     log("timed region done", ms_per_step, "ms/step")
     value = B_total * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # before anything else runs on the device: the last timed step's own results
+        dump_outputs(args.dump_outputs, state["out"])
 
     # informational: spread of repeated short blocks (the timed region above is the contract number)
     block_stats = None
-    if args.blocks > 0:
+    if args.full and args.blocks > 0:
         bl = []
         for _ in range(args.blocks):
             barrier()
@@ -502,75 +553,77 @@ def main():
 
     result = None
     if rank == 0:
-        extras = not args.no_extras
-        # ---- roofline of the dominant kernel (the weighted 8-point fit), HIP events on the launch stream ---------------
-        fit_call = lambda: dfepe.ops.w8pt_forward(m, None, w0, True, W, H, 0.5, True, kind == "train")
-        kdur_us = event_time_us(fit_call)
-        alg_bytes = B * (28 * N + 36)  # read 16N matches + 4N weights; write 36 F + 4N residual + 4N epi  
-        achieved = alg_bytes / (kdur_us * 1e-6) / 1e9
-        # which kernel of the family the library launches for this shape (csrc/w8pt16.hip: use_coop / use_pair2 / LEAN)
-        if N <= dfepe._lib.W8PT16_MAX_N:
-            kname = ("w8pt16_fwd_lean_kernel<raw> (one 16-lane row per pair, 234 registers: two wavefronts per SIMD)" if B >= 12288
-                     else "w8pt16_fwd_kernel<raw> (one 16-lane row per pair, correspondences in registers)")
-        elif N <= 2048 and B <= 1280:
-            kname = "w8pt16_coop_fwd_kernel (a four-wavefront workgroup per pair, correspondences in registers)"
-        elif N <= 2048 and B < 8192:
-            kname = "w8pt16_pair2_fwd_kernel (two 16-lane rows of one wavefront per pair, correspondences re-read per phase)"
-        else:
-            kname = "w8pt16_fwd_kernel<0, raw> (one 16-lane row per pair, correspondences re-read per phase)"
-        row_kernel = N <= dfepe._lib.W8PT16_MAX_N
-        traffic = issue = rocprof_us = rocprof_src = None
-        tpath = os.path.join(REPO, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                traffic = tj.get(f"fit_fwd_B{B}_N{N}")
-                rocprof_us, rocprof_src = tj.get(f"fit_fwd_rocprof_avg_us_B{B}_N{N}"), tj.get("fit_fwd_rocprof_source")
-                valu = tj.get(f"fit_fwd_valu_insts_per_wave_B{B}_N{N}")
-                if valu and row_kernel:
-                    # what actually limits this kernel: four pairs per wavefront, ceil(B / 4 / 1024 SIMDs) wavefronts per SIMD,
-                    # 4 issue cycles per wave64 VALU instruction; instruction count from the committed PMC pass
-                    wps = -(-B // 4096)
-                    cyc = wps * valu * 4.0
-                    clk = tj.get("fit_fwd_sustained_clock_ghz")
-                    # ~5.1 cycles of SIMD time per VALU instruction of this mix (scripts/ubench/lat.hip: fp64 FMA, DPP moves,
-                    # conversions, selects; the same with one or four wavefronts per SIMD) at the sustained clock of the PMC pass
-                    real_us = wps * valu * 5.1 / ((clk or 2.0) * 1e3)
-                    issue = {"valu_insts_per_wave": valu, "waves_per_simd": wps, "cycles": round(cyc),
-                             "floor_us_at_2.4GHz": round(cyc / 2.4e3, 2), "frac_of_kernel_time_at_2.4GHz": round(cyc / 2.4e3 / kdur_us, 3),
-                             "sustained_clock_ghz": clk, "issue_bound_us_at_measured_rate": round(real_us, 2),
-                             "frac_of_kernel_time_at_measured_rate": round(real_us / kdur_us, 3),
-                             "source": "profiles/traffic.json (rocprofv3 --pmc SQ_INSTS_VALU, SQ_BUSY_CU_CYCLES); 5.1 cycles per instruction "
-                                       "from scripts/ubench/lat.hip",
-                             "note": "fraction of this kernel's own instruction stream, NOT a roofline; a lone wavefront per SIMD also pays for "
-                                     "every scalar instruction and branch (~9 cycles each, scripts/ubench/lat2.hip): in round 3 a 14 % cut of "
-                                     "the vector instructions moved the kernel by 3 %, 13 scalar instructions and 3 branches out of each "
-                                     "multisection round by 8 %"}
-            except Exception:
-                traffic = None
-        # the same launch against the ALU peaks ("report both"): arithmetic this algorithm performs per pair, counted from
-        # the kernel: per correspondence ~250 flop (decode, Hartley, 36 fp64 moment FMAs, residual, epipolar residual),
-        # per pair ~9 kflop for the eigen route (Householder tridiagonalisation ~2 k, 16 probes x ~11 rounds x 40 flop of multisection
-        # ~7 k, twisted factorisation + back-transformation + rank-2 step ~1 k); about 70 % of it is fp64
-        flops_pair = 250.0 * N + 9000.0
-        alu_tf = B * flops_pair / (kdur_us * 1e-6) / 1e12
-        alu = {"flops_per_pair": flops_pair, "achieved_TFLOPs": round(alu_tf, 2), "peak_fp64_vector_TFLOPs": 78.6, "frac_of_fp64_peak": round(alu_tf / 78.6, 4),
-               "peak_fp32_vector_TFLOPs": 157.3, "frac_of_fp32_peak": round(alu_tf / 157.3, 4),
-               "note": "useful arithmetic of the tridiagonal eigen route, not issued instructions: the kernel is bound by the in-order issue of ONE "
-                       "wavefront per SIMD (see vector_issue) -- vector instructions, of which data movement inside the row (DPP), selects and "
-                       "conversions are about half, plus the dependency, scalar and branch bubbles nothing else on the SIMD can fill"}
-        roofline = {"bound": "hbm", "kernel": kname, "alu": alu, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
-                    "avg_kernel_us": round(kdur_us, 2), "algorithmic_bytes_per_launch": alg_bytes,
-                    # the same kernel's average in the committed rocprofv3 kernel trace (another box, under the profiler): the two
-                    # methods differ by a few per cent ("say so in the line") -- `frac` is the live HIP-event one
-                    "rocprof_avg_kernel_us": rocprof_us, "rocprof_source": rocprof_src,
-                    "frac_from_rocprof_avg": (round(alg_bytes / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5) if rocprof_us else None),
-                    "launches_per_step": L, "vector_issue": issue,
-                    "traffic_note": "profiles/traffic.json: PMC FETCH_SIZE/WRITE_SIZE of this probe launch, which in the training configs "
-                                    "also writes the 512-B save record per pair on top of the 28N+36 algorithmic bytes",
-                    "method": "HIP events around a hipGraph replay of 50 back-to-back launches on the launch stream, median of 5 replays"}
-        log("roofline probe done", kdur_us)
+        extras = args.full and not args.no_extras
+        roofline = None
+        if args.full:
+            # ---- roofline of the dominant kernel (the weighted 8-point fit), HIP events on the launch stream ---------------
+            fit_call = lambda: dfepe.ops.w8pt_forward(m, None, w0, True, W, H, 0.5, True, kind == "train")
+            kdur_us = event_time_us(fit_call)
+            alg_bytes = B * (28 * N + 36)  # read 16N matches + 4N weights; write 36 F + 4N residual + 4N epi  
+            achieved = alg_bytes / (kdur_us * 1e-6) / 1e9
+            # which kernel of the family the library launches for this shape (csrc/w8pt16.hip: use_coop / use_pair2 / LEAN)
+            if N <= dfepe._lib.W8PT16_MAX_N:
+                kname = ("w8pt16_fwd_lean_kernel<raw> (one 16-lane row per pair, 234 registers: two wavefronts per SIMD)" if B >= 12288
+                         else "w8pt16_fwd_kernel<raw> (one 16-lane row per pair, correspondences in registers)")
+            elif N <= 2048 and B <= 1280:
+                kname = "w8pt16_coop_fwd_kernel (a four-wavefront workgroup per pair, correspondences in registers)"
+            elif N <= 2048 and B < 8192:
+                kname = "w8pt16_pair2_fwd_kernel (two 16-lane rows of one wavefront per pair, correspondences re-read per phase)"
+            else:
+                kname = "w8pt16_fwd_kernel<0, raw> (one 16-lane row per pair, correspondences re-read per phase)"
+            row_kernel = N <= dfepe._lib.W8PT16_MAX_N
+            traffic = issue = rocprof_us = rocprof_src = None
+            tpath = os.path.join(REPO, "profiles", "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    traffic = tj.get(f"fit_fwd_B{B}_N{N}")
+                    rocprof_us, rocprof_src = tj.get(f"fit_fwd_rocprof_avg_us_B{B}_N{N}"), tj.get("fit_fwd_rocprof_source")
+                    valu = tj.get(f"fit_fwd_valu_insts_per_wave_B{B}_N{N}")
+                    if valu and row_kernel:
+                        # what actually limits this kernel: four pairs per wavefront, ceil(B / 4 / 1024 SIMDs) wavefronts per SIMD,
+                        # 4 issue cycles per wave64 VALU instruction; instruction count from the committed PMC pass
+                        wps = -(-B // 4096)
+                        cyc = wps * valu * 4.0
+                        clk = tj.get("fit_fwd_sustained_clock_ghz")
+                        # ~5.1 cycles of SIMD time per VALU instruction of this mix (scripts/ubench/lat.hip: fp64 FMA, DPP moves,
+                        # conversions, selects; the same with one or four wavefronts per SIMD) at the sustained clock of the PMC pass
+                        real_us = wps * valu * 5.1 / ((clk or 2.0) * 1e3)
+                        issue = {"valu_insts_per_wave": valu, "waves_per_simd": wps, "cycles": round(cyc),
+                                 "floor_us_at_2.4GHz": round(cyc / 2.4e3, 2), "frac_of_kernel_time_at_2.4GHz": round(cyc / 2.4e3 / kdur_us, 3),
+                                 "sustained_clock_ghz": clk, "issue_bound_us_at_measured_rate": round(real_us, 2),
+                                 "frac_of_kernel_time_at_measured_rate": round(real_us / kdur_us, 3),
+                                 "source": "profiles/traffic.json (rocprofv3 --pmc SQ_INSTS_VALU, SQ_BUSY_CU_CYCLES); 5.1 cycles per instruction "
+                                           "from scripts/ubench/lat.hip",
+                                 "note": "fraction of this kernel's own instruction stream, NOT a roofline; a lone wavefront per SIMD also pays for "
+                                         "every scalar instruction and branch (~9 cycles each, scripts/ubench/lat2.hip): in round 3 a 14 % cut of "
+                                         "the vector instructions moved the kernel by 3 %, 13 scalar instructions and 3 branches out of each "
+                                         "multisection round by 8 %"}
+                except Exception:
+                    traffic = None
+            # the same launch against the ALU peaks ("report both"): arithmetic this algorithm performs per pair, counted from
+            # the kernel: per correspondence ~250 flop (decode, Hartley, 36 fp64 moment FMAs, residual, epipolar residual),
+            # per pair ~9 kflop for the eigen route (Householder tridiagonalisation ~2 k, 16 probes x ~11 rounds x 40 flop of multisection
+            # ~7 k, twisted factorisation + back-transformation + rank-2 step ~1 k); about 70 % of it is fp64
+            flops_pair = 250.0 * N + 9000.0
+            alu_tf = B * flops_pair / (kdur_us * 1e-6) / 1e12
+            alu = {"flops_per_pair": flops_pair, "achieved_TFLOPs": round(alu_tf, 2), "peak_fp64_vector_TFLOPs": 78.6, "frac_of_fp64_peak": round(alu_tf / 78.6, 4),
+                   "peak_fp32_vector_TFLOPs": 157.3, "frac_of_fp32_peak": round(alu_tf / 157.3, 4),
+                   "note": "useful arithmetic of the tridiagonal eigen route, not issued instructions: the kernel is bound by the in-order issue of ONE "
+                           "wavefront per SIMD (see vector_issue) -- vector instructions, of which data movement inside the row (DPP), selects and "
+                           "conversions are about half, plus the dependency, scalar and branch bubbles nothing else on the SIMD can fill"}
+            roofline = {"bound": "hbm", "kernel": kname, "alu": alu, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic,
+                        "avg_kernel_us": round(kdur_us, 2), "algorithmic_bytes_per_launch": alg_bytes,
+                        # the same kernel's average in the committed rocprofv3 kernel trace (another box, under the profiler): the two
+                        # methods differ by a few per cent ("say so in the line") -- `frac` is the live HIP-event one
+                        "rocprof_avg_kernel_us": rocprof_us, "rocprof_source": rocprof_src,
+                        "frac_from_rocprof_avg": (round(alg_bytes / (rocprof_us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 5) if rocprof_us else None),
+                        "launches_per_step": L, "vector_issue": issue,
+                        "traffic_note": "profiles/traffic.json: PMC FETCH_SIZE/WRITE_SIZE of this probe launch, which in the training configs "
+                                        "also writes the 512-B save record per pair on top of the 28N+36 algorithmic bytes",
+                        "method": "HIP events around a hipGraph replay of 50 back-to-back launches on the launch stream, median of 5 replays"}
+            log("roofline probe done", kdur_us)
 
         acc = {}
         if kind == "train":
@@ -645,7 +698,7 @@ def main():
 
         # ---- CPU baseline: the oracle on a bounded sample of the same workload, on this box's host cores -----------------
         cpu = None
-        if not args.no_cpu_baseline and world == 1:  # contract: CPU baseline on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # contract: CPU baseline on rank 0 at N=1 only
             import numpy as np
 
             oracle = importlib.import_module("oracle.deepf_oracle")
@@ -827,6 +880,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup, "spinup_steps": args.spinup,
+            "full": args.full,  # false: the informational fields below are null (run with --full to measure them)
             "ms_per_step": round(ms_per_step, 4),
             "ms_per_step_per_rank": per_rank_ms,
             "rccl_world_size": rccl_world,

@@ -12,7 +12,7 @@ if [ "$1" = build ]; then
 fi
 for b in 4096 512; do
   for L in pytorch-deepfepe_amd/libdfepe_hip.so ab_libs/libdfepe_cheir_FAST.so ab_libs/libdfepe_cheir_SLOW.so; do
-    DFEPE_LIB_PATH=$(realpath $L) timeout 200 python bench.py --config 5 --batch $b --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    DFEPE_LIB_PATH=$(realpath $L) timeout 200 python bench.py --config 5 --batch $b --full --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$b', '$(basename $L)', 'ms', d['ms_per_step'], 'fit_us', d['roofline']['avg_kernel_us'], d['accuracy'].get('pairs_with_a_valid_pose'))"
   done
 done

@@ -6,7 +6,7 @@ O=gpurun_out/final; mkdir -p $O
 timeout 900 python -m pytest tests -x -q -m gpu < /dev/null > $O/gpu_suite.log 2>&1; echo "pytest rc=$?" ; tail -3 $O/gpu_suite.log
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" < /dev/null > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 < /dev/null > $O/bench_driver.json 2> $O/bench_driver.err; echo "bench(driver flags) rc=$?"
-timeout 300 python bench.py < /dev/null > $O/bench_default.json 2> $O/bench_default.err; echo "bench(default) rc=$?"
+timeout 300 python bench.py --full < /dev/null > $O/bench_default.json 2> $O/bench_default.err; echo "bench(default) rc=$?"
 timeout 200 python bench.py --gpus 1 --force-dist --steps 20 --warmup 5 --no-extras --no-cpu-baseline < /dev/null > $O/bench_dist.json 2> $O/bench_dist.err; echo "bench(force-dist) rc=$?"
 for f in bench_driver bench_default bench_dist; do python - "$O/$f.json" <<'PY'
 import json, sys

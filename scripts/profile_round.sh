@@ -5,7 +5,7 @@
 TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$TAG; rm -rf $O; mkdir -p $O
-timeout 280 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --steps 200 --warmup 20 --cpu-sample 128 > $O/bench_trace.log 2>&1
+timeout 280 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --full --steps 200 --warmup 20 --cpu-sample 128 > $O/bench_trace.log 2>&1
 grep '^{"metric"' $O/bench_trace.log > $O/bench_line.json
 pmc() { name=$1; shift; timeout 150 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/pmc_$name -o p -- python $R/scripts/pmc_probe.py > $O/pmc_$name.log 2>&1; }
 pmc fetch FETCH_SIZE
