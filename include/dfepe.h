@@ -596,6 +596,54 @@ int dfepe_gather_matches(const float *pts1, const float *pts2, const float *off1
                          const int *m_idx1, const int *m_idx2, const float *score, const int *choice, int n_out,
                          float *xs, float *offsets, float *quality, void *stream);
 
+/*
+ * Robust fundamental matrix of every pair: OpenCV 3.4 findFundamentalMat(x1, x2, FM_RANSAC, threshold, confidence, max_iters),
+ * batched.  Replaces: cv2.findFundamentalMat(x1, x2, cv2.RANSAC, 0.1) in utils_opencv.recover_camera_opencv
+ * (deepFEPE/dsac_tools/utils_opencv.py:157), the validation baseline of val_rt (train_good_utils.py:615-633).
+ *   matches [B,N,4] fp32 pixels (x1, y1, x2, y2), 16-byte aligned; 15 <= N <= 4096 (N < 15: DFEPE_ERR_UNSUPPORTED -- OpenCV
+ *     switches to LMedS there, which is not built; N > 4096: the pair does not fit in LDS); B <= 65535 (else UNSUPPORTED)
+ *   threshold t (pixels, >= 0), confidence p in [0, 1], max_iters >= 1, seed: see the algorithm below
+ *   workspace  dfepe_ransac_workspace_bytes(B, N, max_iters) bytes of device memory, 16-byte aligned, overwritten
+ *   F_out [B,9] fp32 (F22 = 1; zeros when the pair has no model); inlier_mask [B,N] uint8; n_inliers [B] int32 (0: no model);
+ *   iters_run [B] int32 (iterations consumed); best_hyp [B,2] int32 (winning iteration and root, -1 -1 without a model; may be
+ *   NULL); hyp_counts [B,max_iters,3] int32 or NULL: the count table (inliers of root r of iteration k; -1 = no such root,
+ *   -2 = the iteration drew no sample); masked_matches [B,N,4] or NULL: the matches with every non-inlier row set to quiet NaN
+ *   (the `mask=` input of cv2.recoverPose for dfepe_cheirality_ex: a NaN row passes no depth test).
+ * The algorithm (sequential definition; the device evaluates all max_iters iterations in parallel and applies this rule to the
+ * counts, with the same result):
+ *   1 Sampling.  Iteration k draws indices from the stream s_k: draw c is splitmix64(key_k + c * 0x9E3779B97F4A7C15) with
+ *     key_k = splitmix64(seed ^ splitmix64(k)), mapped to [0, N) by Lemire's multiply-shift of its upper 32 bits.  The stream
+ *     does not depend on the pair (OpenCV re-seeds its RNG with a constant on every call), so a pair's result does not depend on
+ *     the batch around it.  7 distinct indices; a sample that fails OpenCV's haveCollinearPoints test for its last point in
+ *     either image (|dx2 dy1 - dy2 dx1| <= FLT_EPSILON (|dx1| + |dy1| + |dx2| + |dy2|), non-partial checkSubset) is redrawn from
+ *     the same stream; after 1000 attempts the iteration has no sample, the loop ends there, and with k = 0 there is no model.
+ *   2 7-point solve in fp64 on the sample normalised per image (centroid 0, RMS distance sqrt(2)): null space {F1, F2} of the
+ *     7x9 system with rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1] (Householder QR), real roots of
+ *     det(l F1 + (1 - l) F2) = 0 ascending (one or three), each F de-normalised and scaled to F22 = 1 where |F22| > DBL_EPSILON.
+ *   3 Score: a correspondence is an inlier iff max(d1^2, d2^2) <= t^2 (d2: distance of x2 to the line F x1, d1: of x1 to
+ *     F^T x2; OpenCV's FMEstimatorCallback::computeError), evaluated in fp64 on the pixel coordinates without divisions.
+ *     Decisions can differ from an exact evaluation only inside a relative band of 1e-6 around t^2.
+ *   4 Select: through k = 0, 1, ... and the roots in order, a model whose count exceeds max(best, 6) becomes the best, and
+ *     niters = RANSACUpdateNumIters(p, (N - count) / N, 7, niters); the loop stops at k >= niters (niters starts at max_iters).
+ *     RANSACUpdateNumIters: num = log(max(1 - p, DBL_MIN)), den = 1 - (1 - ep)^7; den < DBL_MIN: 0; otherwise with
+ *     den = log(den): den >= 0 or -num >= niters (-den) ? niters : rint(num / den).
+ */
+size_t dfepe_ransac_workspace_bytes(int B, int N, int max_iters);
+int dfepe_ransac_fundamental(const float *matches, int B, int N, double threshold, double confidence, int max_iters,
+                             unsigned long long seed, void *workspace, float *F_out, unsigned char *inlier_mask, int *n_inliers,
+                             int *iters_run, int *best_hyp, int *hyp_counts, float *masked_matches, void *stream);
+/*
+ * Which correspondences the winning pose candidate sees in front of both cameras (cv2.recoverPose's output mask, `mask2` of
+ * utils_opencv.recover_camera_opencv, deepFEPE/dsac_tools/utils_opencv.py:177,208).
+ *   E, K [B,9]: the matrices handed to dfepe_cheirality_ex (pre = NULL); matches [B,N,4] the same matches (NaN rows: 0), 16-byte
+ *   aligned; B <= 65535 (else UNSUPPORTED);
+ *   winner [B] its winner output (-1: all zeros); mask [B,N] uint8.
+ * The test of every correspondence is the fp64 route of dfepe_cheirality_ex (same rows, normal matrix, eigenvector refinement and
+ * depth tests), so the number of ones in a row of mask equals counts[winner] of that call.
+ */
+int dfepe_ransac_in_front(const float *E, const float *K, const float *matches, int B, int N, float depth_thres, const int *winner,
+                          unsigned char *mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

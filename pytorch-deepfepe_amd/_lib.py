@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint, c_ulonglong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DFEPE_LIB_PATH: another build of the same library (scripts/ab_step.sh times two builds alternately on one box)
@@ -25,6 +25,7 @@ W8PT16_MAX_N = 128
 TAIL_MAX_LAYERS = 16  # dfepe_loss_tail: layers per launch (kTailMaxLayers, csrc/loss_tail_body.h)
 EPI_HOMOGENEOUS = 8
 CHEIR_FP64_ONLY = 1
+RANSAC_MIN_N = 15  # dfepe_ransac_fundamental: below, OpenCV switches to LMedS (not built)
 
 _P = c_void_p
 _SIGNATURES = {
@@ -98,6 +99,9 @@ _SIGNATURES = {
     "dfepe_nn_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_nn_match_two_way": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P]),
     "dfepe_gather_matches": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    "dfepe_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_ransac_fundamental": (c_int, [_P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfepe_ransac_in_front": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -410,18 +410,18 @@ def val_rt(idx, K_np, x1_single_np, x2_single_np, E_est_np, E_gt_np, F_est_np, F
     """Same call and same 9-tuple as the reference's per-pair validation worker (train_good_utils.py:553-646):
     (error_Rt_estW, epi_dist_mean_estW, error_Rt_opencv, epi_dist_mean_opencv, error_Rt_gt, epi_dist_mean_gt, idx, M_estW, M_opencv).
     The estimated-E and ground-truth-E legs go through utils_F.goodCorr_eval_nondecompose (the cheirality kernel in place of
-    cv2.recoverPose) and utils_F.epi_distance_np.  The OpenCV five-point / eight-point RANSAC baseline (``if_opencv``,
-    utils_opencv.recover_camera_opencv) is outside this build (OpenCV baselines): its three slots are None.
-    ``if_opencv`` keeps the reference's default (True); a caller that asks for the OpenCV leg -- explicitly or by that default --
-    gets one warning saying that its slots stay None, instead of an unrelated TypeError when it indexes them later.
+    cv2.recoverPose) and utils_F.epi_distance_np.  The OpenCV baseline (``if_opencv``, default True like the reference):
+    with five_point=False its three slots are filled as the reference fills them (:615-633) by compat.utils_opencv.
+    recover_camera_opencv (the batched RANSAC 8-point estimator + E projection + masked pose); the five-point solver is not
+    built, so five_point=True gets one warning and None slots, instead of an unrelated TypeError when they are indexed later.
     One pair per call like the reference; val_rt_batch / validation_summary below are the batched forms."""
-    from . import utils_F
+    from . import utils_F, utils_opencv
 
     global _warned_opencv
-    if if_opencv and not _warned_opencv:
+    if if_opencv and five_point and not _warned_opencv:
         import warnings
 
-        warnings.warn("val_rt(if_opencv=True): the OpenCV five-point / RANSAC baseline is not part of this build (SURVEY.md §2); "
+        warnings.warn("val_rt(if_opencv=True, five_point=True): the OpenCV five-point baseline is not part of this build (SURVEY.md §2); "
                       "error_Rt_opencv, epi_dist_mean_opencv and M_opencv are returned as None", RuntimeWarning, stacklevel=2)
         _warned_opencv = True
 
@@ -432,16 +432,24 @@ def val_rt(idx, K_np, x1_single_np, x2_single_np, E_est_np, E_gt_np, F_est_np, F
                                                             delta_Rtij_inv, K_np, None)
     epi_dist_mean_estW, _, _ = utils_F.epi_distance_np(F_est_np, x1_single_np, x2_single_np, if_homo=False)
     epi_dist_mean_gt, _, _ = utils_F.epi_distance_np(F_gt_np, x1_single_np, x2_single_np, if_homo=False)
-    return (error_Rt_estW, epi_dist_mean_estW, None, None, error_Rt_gt, epi_dist_mean_gt, idx, M_estW, None)
+    error_Rt_opencv = epi_dist_mean_opencv = M_opencv = None
+    if if_opencv and not five_point:
+        M_opencv, error_Rt_opencv, _, E_return = utils_opencv.recover_camera_opencv(K_np, x1_single_np, x2_single_np, delta_Rtij_inv,
+                                                                                    five_point=False, threshold=0.01, show_result=False)
+        epi_dist_mean_opencv, _, _ = utils_F.epi_distance_np(E_return[1], x1_single_np, x2_single_np, if_homo=False)
+    return (error_Rt_estW, epi_dist_mean_estW, error_Rt_opencv, epi_dist_mean_opencv, error_Rt_gt, epi_dist_mean_gt, idx, M_estW, M_opencv)
 
 
-def val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=True, depth_thres=50.0):
+def val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=True, depth_thres=50.0, baseline=False):
     """Batched GPU counterpart of the validation fan-out (Train_model_pipeline.py:954-964,1048-1061 -> val_rt :553-646 ->
     utils_F.goodCorr_eval_nondecompose -> cv2.recoverPose): optional projection of E onto singular values (1,1,0),
     cheirality-checked pose for every pair, rotation / translation angular errors against the ground-truth camera motion.
     Ks, E_ests [B,3,3]; matches_xy [B,N,4] pixels; delta_Rtijs_4_4 [B,4,4] (scene motion, like the dataset).
     Returns dict(err_R_deg [B], err_t_deg [B], Rt_cam [B,3,4], winner [B], counts [B,4]); pairs without a valid
-    candidate get the reference's failure values 180 / 90 degrees."""
+    candidate get the reference's failure values 180 / 90 degrees.
+    ``baseline``: also the OpenCV 8-point baseline of every pair (val_rt's if_opencv leg, utils_opencv.recover_camera_opencv:
+    ops.ransac_pose with the reference's 0.1 px and its recoverPose camera), under the keys err_R_deg_opencv, err_t_deg_opencv,
+    Rt_cam_opencv, winner_opencv, F_opencv, E_opencv, inlier_mask_opencv."""
     E = E_ests.float()
     if not E.is_cuda:
         raise _lib.DfepeError("val_rt_batch: tensors must live on the GPU")
@@ -455,22 +463,43 @@ def val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=True, depth_
     bad = win < 0
     err_R = torch.where(bad, torch.full_like(err_R, 180.0), err_R)
     err_t = torch.where(bad, torch.full_like(err_t, 90.0), err_t)
-    return {"err_R_deg": err_R, "err_t_deg": err_t, "Rt_cam": Rt, "winner": win, "counts": cnt}
+    out = {"err_R_deg": err_R, "err_t_deg": err_t, "Rt_cam": Rt, "winner": win, "counts": cnt}
+    if baseline:
+        from .utils_opencv import BASELINE_THRESHOLD, recover_pose_camera
+
+        K = Ks.to(dev).float()
+        b = ops.ransac_pose(matches_xy.to(dev), K, threshold=BASELINE_THRESHOLD, K_pose=recover_pose_camera(K))
+        Rb = b["Rt_cam"]
+        eR = ops.rot_angle_deg(Rb[:, :, :3].contiguous(), gt[:, :3, :3].contiguous())
+        et = ops.vector_angle_deg(Rb[:, :, 3].contiguous(), gt[:, :3, 3].contiguous())
+        bad = b["winner"] < 0
+        out.update({"err_R_deg_opencv": torch.where(bad, torch.full_like(eR, 180.0), eR),
+                    "err_t_deg_opencv": torch.where(bad, torch.full_like(et, 90.0), et),
+                    "Rt_cam_opencv": Rb, "winner_opencv": b["winner"], "F_opencv": b["F"], "E_opencv": b["E"],
+                    "inlier_mask_opencv": b["mask"]})
+    return out
 
 
-def validation_summary(Ks, matches_xy, E_ests, F_ests, F_gts, delta_Rtijs_4_4, project_E=True, depth_thres=50.0):
+def validation_summary(Ks, matches_xy, E_ests, F_ests, F_gts, delta_Rtijs_4_4, project_E=True, depth_thres=50.0, baseline=False):
     """One validation batch end to end on the device: val_rt_batch (pose errors of every pair), the epipolar distances of
     every correspondence under the estimated and the ground-truth F (epi_distance_np: d1 + d2, utils_F.py:363-385, as val_rt
     calls it, train_good_utils.py:609-614), and the reductions write_metrics_summary applies to them (:758-856).
-    Returns (summary dict of python floats for the 'ours' tag, per-pair dict of device tensors)."""
+    Returns (summary dict of python floats for the 'ours' tag, per-pair dict of device tensors).
+    ``baseline``: val_rt_batch's OpenCV 8-point baseline too, its epipolar distances (per-pair key epi_dists_opencv) and its
+    summary (key "opencv_8p" of the summary dict, the reference's tag for it)."""
     from . import utils_F
 
-    pairs = val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=project_E, depth_thres=depth_thres)
+    pairs = val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=project_E, depth_thres=depth_thres, baseline=baseline)
     X, Y = matches_xy[:, :, :2].contiguous(), matches_xy[:, :, 2:].contiguous()
     d_est = 2.0 * utils_F._epi_distance(F_ests, X, Y)[0]  # (d1 + d2), the first return value of epi_distance_np
     d_gt = 2.0 * utils_F._epi_distance(F_gts, X, Y)[0]
     pairs.update({"epi_dists": d_est, "epi_dists_gt": d_gt})
-    return ops.metrics_summary(d_est, d_gt, pairs["err_R_deg"], pairs["err_t_deg"]), pairs
+    summary = ops.metrics_summary(d_est, d_gt, pairs["err_R_deg"], pairs["err_t_deg"])
+    if baseline:
+        d_ocv = 2.0 * utils_F._epi_distance(pairs["F_opencv"], X, Y)[0]
+        pairs["epi_dists_opencv"] = d_ocv
+        summary["opencv_8p"] = ops.metrics_summary(d_ocv, d_gt, pairs["err_R_deg_opencv"], pairs["err_t_deg_opencv"])
+    return summary, pairs
 
 
 def write_metrics_summary(writer, dict_of_lists, task, n_iter):

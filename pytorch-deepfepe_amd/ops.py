@@ -933,6 +933,74 @@ def fit_pose(matches: Tensor, weights: Tensor, K: Tensor, image_w: float, image_
     return F, residual, epi, w_out, Rt, win, cnt
 
 
+def ransac_fundamental(matches: Tensor, threshold: float = 0.1, confidence: float = 0.99, max_iters: int = 1000, seed: int = 0,
+                       want_hyp_counts: bool = False, want_masked: bool = False):
+    """matches [B,N,4] pixels -> robust F of every pair by OpenCV 3.4's findFundamentalMat(FM_RANSAC) algorithm (the validation
+    baseline, utils_opencv.py:157; include/dfepe.h spells out the sampler, the 7-point solve, the error and the stopping rule).
+    Returns dict(F [B,3,3] (F22 = 1; zeros without a model), mask [B,N] uint8, n_inliers [B], iters_run [B], best_hyp [B,2]
+    (iteration, root; -1 without a model), hyp_counts [B,max_iters,3] | None (-1: no root, -2: no sample), masked [B,N,4] | None
+    (non-inlier rows NaN)).  No host synchronisation.  15 <= N <= 4096: below 15 OpenCV runs LMedS, which is not built."""
+    m = _prep(matches, "matches")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    B, N = m.shape[0], m.shape[1]
+    if N < _lib.RANSAC_MIN_N:
+        raise _lib.DfepeError(f"ransac_fundamental: {N} correspondences per pair; the RANSAC estimator needs at least "
+                              f"{_lib.RANSAC_MIN_N} (OpenCV switches to LMedS below that, which is not built)")
+    L = _lib.lib()
+    dev = m.device
+    ws = torch.empty(max(1, (int(L.dfepe_ransac_workspace_bytes(B, N, int(max_iters))) + 15) // 16), 2, dtype=torch.float64, device=dev)
+    out = {
+        "F": torch.empty(B, 3, 3, device=dev),
+        "mask": torch.empty(B, N, device=dev, dtype=torch.uint8),
+        "n_inliers": torch.empty(B, device=dev, dtype=torch.int32),
+        "iters_run": torch.empty(B, device=dev, dtype=torch.int32),
+        "best_hyp": torch.empty(B, 2, device=dev, dtype=torch.int32),
+        "hyp_counts": torch.empty(B, int(max_iters), 3, device=dev, dtype=torch.int32) if want_hyp_counts else None,
+        "masked": torch.empty(B, N, 4, device=dev) if want_masked else None,
+    }
+    with _on(dev):
+        rc = L.dfepe_ransac_fundamental(_ptr(m), B, N, float(threshold), float(confidence), int(max_iters), int(seed) & ((1 << 64) - 1),
+                                        _ptr(ws), _ptr(out["F"]), _ptr(out["mask"]), _ptr(out["n_inliers"]), _ptr(out["iters_run"]),
+                                        _ptr(out["best_hyp"]), _ptr(out["hyp_counts"]), _ptr(out["masked"]), _stream())
+    _lib.check(rc, "dfepe_ransac_fundamental")
+    return out
+
+
+def ransac_in_front(E: Tensor, K: Tensor, matches: Tensor, winner: Tensor, depth_thres: float = 50.0) -> Tensor:
+    """[B,N] uint8: the correspondences the winning candidate of cheirality(E, K, matches, depth_thres) sees in front of both
+    cameras (cv2.recoverPose's mask output); a row sums to that call's counts[winner]."""
+    E, K, m = _prep(E, "E"), _prep(K, "K"), _prep(matches, "matches")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    B, N = m.shape[0], m.shape[1]
+    _shape(E, "E", B, 3, 3)
+    _shape(K, "K (one intrinsic matrix per pair)", B, 3, 3)
+    if winner.shape != (B,) or winner.dtype != torch.int32 or not winner.is_contiguous():
+        raise ValueError("winner must be the contiguous [B] int32 output of cheirality")
+    mask = torch.empty(B, N, device=m.device, dtype=torch.uint8)
+    with _on(m.device):
+        rc = _lib.lib().dfepe_ransac_in_front(_ptr(E), _ptr(K), _ptr(m), B, N, float(depth_thres), _ptr(winner), _ptr(mask), _stream())
+    _lib.check(rc, "dfepe_ransac_in_front")
+    return mask
+
+
+def ransac_pose(matches: Tensor, K: Tensor, threshold: float = 0.1, confidence: float = 0.99, max_iters: int = 1000, seed: int = 0,
+                depth_thres: float = 50.0, K_pose: Optional[Tensor] = None):
+    """The 8-point baseline of utils_opencv.recover_camera_opencv (utils_opencv.py:157-177) for every pair: ransac_fundamental,
+    E = K^T F K projected onto singular values (1, 1, 0), then cv2.recoverPose(E, x1, x2, camera K_pose, mask=inliers): the
+    unchanged cheirality kernel on the matches with the non-inlier rows set to NaN (a NaN row passes no depth test).
+    K_pose: the camera recoverPose is given (default K; the reference passes focal K[0,0] and principal point (K[0,2], K[1,2])).
+    Returns the ransac_fundamental dict with E [B,3,3], Rt_cam [B,3,4], winner [B], counts [B,4] and in_front [B,N] uint8 added."""
+    K = _prep(K, "K")
+    out = ransac_fundamental(matches, threshold, confidence, max_iters, seed, want_masked=True)
+    B = out["F"].shape[0]
+    _shape(K, "K (one intrinsic matrix per pair)", B, 3, 3)
+    Kp = K if K_pose is None else _prep(K_pose, "K_pose")
+    E = project_essential(congruence(out["F"], K))
+    Rt, win, cnt = cheirality(E, Kp, out["masked"], depth_thres)
+    out.update({"E": E, "Rt_cam": Rt, "winner": win, "counts": cnt, "in_front": ransac_in_front(E, Kp, out["masked"], win, depth_thres)})
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # validation summary reductions ("next" row f-2)
 # ------------------------------------------------------------------------------------------------
