@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ransac_ref as ref  # noqa: E402
+import test_ransac_edges_gpu as edges  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -45,38 +46,21 @@ def test_noise_free_pairs_stop_after_the_first_model(dfepe):
 @pytest.fixture(scope="module")
 def outlier_run(dfepe):
     sc = _scene(dfepe, 2, 1000, 5, 0.4)
-    m = sc["matches_xy_ori"]
-    out = dfepe.ops.ransac_fundamental(m.to(DEV), threshold=1.0, max_iters=1000, seed=3, want_hyp_counts=True)
-    torch.cuda.synchronize()
-    return m.numpy(), {k: (v.cpu().numpy() if v is not None else None) for k, v in out.items()}
+    m = sc["matches_xy_ori"].numpy()
+    out = edges.run(dfepe, m, 1.0, 0.99, 1000, 3)  # also: the workspace table gives bit-identical outputs
+    return m, out, [ref.hypotheses(m[b], 3, 1000) for b in range(m.shape[0])]
 
 
 def test_count_table_against_the_fp64_restatement(outlier_run):
-    m, out = outlier_run
-    t2 = 1.0
+    m, out, hyps = outlier_run
     for b in range(m.shape[0]):
-        tab = out["hyp_counts"][b]
-        n_cmp = n_rootcount_diff = 0
-        for k, (idx, Fs) in enumerate(ref.hypotheses(m[b], 3, 1000)):
-            row = tab[k]
-            if idx is None:
-                assert (row == ref.NO_SAMPLE).all()
-                continue
-            dev = sorted(int(c) for c in row if c >= 0)
-            assert (row[len(dev):] == ref.NO_ROOT).all()  # roots first, absent ones after
-            if len(dev) != len(Fs):
-                n_rootcount_diff += 1
-                continue
-            errs = [ref.errors(F, m[b]) for F in Fs]
-            counts = sorted(int((e <= t2).sum()) for e in errs)
-            band = max(int((np.abs(e - t2) <= BAND * t2).sum()) for e in errs)
-            assert all(abs(a - c) <= band for a, c in zip(dev, counts)), (b, k, dev, counts, band)
-            n_cmp += 1
-        assert n_rootcount_diff <= 0.001 * 1000 + 1 and n_cmp > 900
+        verdict, n_cmp = edges.check_pair(m, out, b, 1.0, 0.99, 3, 1000, hyps[b])
+        assert n_cmp > 900
+        assert verdict == "exact"  # the rule over the restatement's own table reaches the device's count, iteration and stop
 
 
 def test_selection_and_mask_follow_the_sequential_rule(outlier_run):
-    m, out = outlier_run
+    m, out, hyps = outlier_run
     t2 = 1.0
     for b in range(m.shape[0]):
         best, bk, br, iters = ref.select(out["hyp_counts"][b], m.shape[1], 0.99, 1000)
@@ -87,10 +71,11 @@ def test_selection_and_mask_follow_the_sequential_rule(outlier_run):
         err = ref.errors(out["F"][b].astype(np.float64), m[b])
         sure = np.abs(err - t2) > BAND * t2
         assert ((mask == 1) == (err <= t2))[sure].all()
-        # the winner is the model of that iteration's sample
-        idx = ref.draw_sample(3, bk, m[b])
-        Fr = ref.seven_point(m[b][idx])
-        assert min(np.linalg.norm(unit(out["F"][b]) - unit(F)) for F in Fr) < 1e-5
+        # the winner is the root of that iteration's sample whose count is n_inliers
+        idx, Fr = hyps[b][bk]
+        assert idx == ref.draw_sample(3, bk, m[b])
+        Fc = [F for F in Fr if int((ref.errors(F, m[b]) <= t2).sum()) == best]
+        assert Fc and min(np.linalg.norm(unit(out["F"][b]) - unit(F)) for F in Fc) < 1e-5
 
 
 def test_pose_on_the_nan_masked_matches(dfepe):
