@@ -1,8 +1,14 @@
 """The reference-API mirror (pytorch-deepfepe_amd/compat) against golden vectors produced by the reference itself
 and against the CPU oracle.  GPU box only."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cheirality_cases as cc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 IMAGE_SIZE = [376, 1241, 3]
@@ -392,10 +398,14 @@ def test_cheirality_recovers_generating_pose(dfepe, oracle, N):
         assert win[b] >= 0 and cnt[b].max() == cnt[b, win[b]]
         assert oracle.rotation_angle_deg(Rt[b, :, :3], cam[b, :3, :3]) < 0.05
         assert oracle.vector_angle_deg(Rt[b, :, 3], cam[b, :3, 3]) < 0.5
-    for b in range(3):  # counts against the CPU DLT (same algorithm, fp64 SVD of the 4x4)
-        _, _, counts = oracle.cheirality_select(E[b].double(), sc["Ks"][b].numpy(), sc["matches_xy_ori"][b, :, :2].double().numpy(),
-                                                sc["matches_xy_ori"][b, :, 2:].double().numpy(), 50.0)
-        assert sorted(counts) == sorted(cnt[b].tolist()) or np.abs(np.sort(counts) - np.sort(cnt[b])).max() <= max(1, N // 200)
+    # every pair per correspondence against the fp64 restatement (tests/cheirality_ref.py), and the oracle's counts (same
+    # algorithm, LAPACK SVD of the 4x4) tied to it
+    Ef, Kf, mf = E.float().to(DEV), sc["Ks"].float().to(DEV), sc["matches_xy_ori"].float().to(DEV)
+    refs, xs = cc.check_cheirality(dfepe, None, Ef, Kf, mf, 50.0, dfepe.ops.cheirality(Ef, Kf, mf, 50.0))
+    for b in range(3):
+        _, _, counts = oracle.cheirality_select(Ef[b].cpu().double(), Kf[b].cpu().double().numpy(), mf[b, :, :2].cpu().double().numpy(),
+                                                mf[b, :, 2:].cpu().double().numpy(), 50.0)
+        cc.hold_lapack_counts(refs[b], xs[b], cnt[b], counts, f"pair {b}")
     # compat wrapper returns the reference's triple
     _, err, Rt_cam = dfepe.compat.utils_F._E_to_M_train(E[0].to(DEV), sc["Ks"][0].numpy(), sc["matches_xy_ori"][0, :, :2].numpy(),
                                                         sc["matches_xy_ori"][0, :, 2:].numpy(), delta_Rt_gt_cam=cam[0], show_result=False)
@@ -406,8 +416,9 @@ def test_cheirality_recovers_generating_pose(dfepe, oracle, N):
 def test_cheirality_matches_the_references_own_logic(dfepe, golden, case, pad_to):
     """dfepe_cheirality against tests/golden/cheirality.npz -- the reference's own _E_to_M_train (utils_F.py:679-763:
     candidate order, 0 < Z < depth_thres in both cameras, first arg-max, _inv_Rt of the winner) run with a DLT stand-in for
-    cv2.triangulatePoints.  The winner's count and Rt_cam must agree; a count may differ by the odd correspondence whose
-    depth sits on a bound (the 4x4 eigen-solver here is not numpy's SVD; OpenCV's own triangulation is unpinned anyway).
+    cv2.triangulatePoints.  Every candidate's per-correspondence decisions, the counts, the winner and Rt_cam must agree with the
+    fp64 restatement (cheirality_cases.check_cheirality) and through it with the golden's counts: exactly, except at correspondences
+    within the restatement's derived band of a bound (OpenCV's own triangulation is unpinned anyway).
     pad_to > 2048 embeds the fixture pairs in a large batch: that selects the one-wavefront-per-pair variant at N = 1000."""
     g = golden("cheirality")
     E, K, m = (torch.from_numpy(g[f"{case}_{k}"]).float() for k in ("E", "K", "matches"))
@@ -417,23 +428,29 @@ def test_cheirality_matches_the_references_own_logic(dfepe, golden, case, pad_to
         sc = dfepe.synth.make_scene(pad_to - Bf, N, seed=9, outlier_ratio=0.2)
         Ef = sc["E_gt"] / sc["E_gt"].flatten(1).norm(dim=1)[:, None, None]
         E, K, m = torch.cat((E, Ef.float())), torch.cat((K, sc["Ks"].float())), torch.cat((m, sc["matches_xy_ori"].float()))
-    Rt, win, cnt = dfepe.ops.cheirality(E.to(DEV), K.to(DEV), m.to(DEV), thr)
-    Rt, win, cnt = Rt.cpu().numpy()[:Bf], win.cpu().numpy()[:Bf], cnt.cpu().numpy()[:Bf]
+    out = dfepe.ops.cheirality(E.to(DEV), K.to(DEV), m.to(DEV), thr)
+    Rt, win, cnt = (t.cpu().numpy()[:Bf] for t in out)
     gc, gw, gR = g[f"{case}_counts"], g[f"{case}_winner"], g[f"{case}_Rt_cam"]
     # The ORDER of the four candidates follows the SVD gauge (the signs LAPACK happens to give u3 and (u1, v1) decide which
-    # candidate is "(R1, t)"; any valid SVD yields the same SET), so per-candidate counts are compared as a multiset and the
-    # winner through what it selects: its count and its pose, both gauge-free.
-    slack = max(1, N // 250)
-    assert np.abs(np.sort(cnt, axis=1) - np.sort(gc, axis=1)).max() <= slack, (cnt, gc)
+    # candidate is "(R1, t)"; any valid SVD yields the same SET): check_cheirality resolves it per pair from the winner's pose and
+    # holds every candidate's per-correspondence mask, count, the vote and the pose to the fp64 restatement; the golden's own
+    # counts (numpy's SVD in the same algorithm) lie in the restatement's intervals and, where nothing is undecided, ARE the
+    # device's counts under that gauge.
+    refs, xs = cc.check_cheirality(dfepe, None, E[:Bf].to(DEV), K[:Bf].to(DEV), m[:Bf].to(DEV), thr, tuple(t[:Bf] for t in out))
+    margin = max(2, N // 125)  # a vote the golden decides by more than this was always held to the golden's pose
     decided = 0
     for b in range(Bf):
+        cc.hold_lapack_counts(refs[b], xs[b], cnt[b], gc[b], f"{case} pair {b}")
         top2 = np.sort(gc[b])[-2:]
         if gw[b] < 0:
             assert win[b] < 0
             continue
-        assert win[b] >= 0 and abs(int(cnt[b, win[b]]) - int(gc[b, gw[b]])) <= slack
-        if top2[1] - top2[0] > 2 * slack:  # a decided vote: the winner is not up to a boundary point
+        assert win[b] >= 0
+        # the winning counts: equal, up to the correspondences the restatement leaves undecided (none in most pairs)
+        assert abs(int(cnt[b, win[b]]) - int(gc[b, gw[b]])) <= int(refs[b]["undecided"].sum())
+        if top2[1] - top2[0] > margin or (top2[1] > top2[0] and not refs[b]["undecided"].any()):
             decided += 1
+            assert win[b] ^ xs[b] == gw[b]
             np.testing.assert_allclose(Rt[b], gR[b], atol=2e-5)
     assert decided >= Bf // 2
 

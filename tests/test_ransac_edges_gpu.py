@@ -17,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ransac_ref as ref  # noqa: E402
+from cheirality_cases import scaled_y as _scaled_y  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -352,17 +353,6 @@ def check_in_front(oracle, E, Kp, m, Rt_cam, mask, depth_thres=50.0):
     got = np.asarray(mask) == 1
     assert (got == want)[sure].all(), np.nonzero((got != want) & sure)[0][:10]
     return int(sure.sum())
-
-
-def _scaled_y(sc, s=1.25):
-    """The scene seen by a camera with fy = s fx: y pixel coordinates and K's second row scaled by s (F and the pose unchanged
-    in the normalised frame)."""
-    m = sc["matches_xy_ori"].clone()
-    m[..., 1] *= s
-    m[..., 3] *= s
-    K = sc["Ks"].clone()
-    K[:, 1] *= s
-    return m.contiguous(), K.contiguous()
 
 
 @pytest.mark.parametrize("N,B,camera", [(15, 3, "K"), (63, 70, "pose_camera"), (64, 1, "identity"), (65, 3, "K"),
