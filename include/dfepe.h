@@ -54,7 +54,9 @@ extern "C" {
                                      _F_from_XY, utils_F.py:116-119,233-236)                                 */
 
 #define DFEPE_W8PT_ROW_PER_PAIR 64u /* scheduling only, same function, same `save` record: never spread a pair over the 16 rows of
-                                       a cooperative workgroup (what the library does for 128 < N <= 2048 below 3072 pairs);
+                                       a cooperative workgroup (what the library does for 128 < N <= 2048: the forward fit of pixel
+                                       matches up to 1280 pairs, of homogeneous points and the backward fit up to 3072; the rule
+                                       is pytorch-deepfepe_amd/csrc/fit_plan.h);
                                        one 16-lane row per pair, correspondences re-read per phase.  A/B timing; pass the same
                                        bit to dfepe_w8pt_bwd or not, the record format does not depend on it.             */
 #define DFEPE_W8PT_ALL_FLAGS 127u   /* any other bit in `flags` is DFEPE_ERR_INVALID_ARG                              */
@@ -290,8 +292,9 @@ int dfepe_cheirality_ex(const float *E, const float *pre, const float *K, const 
  * Fit + E-from-F + cheirality-checked pose in one call (BASELINE config 5: one weighted 8-point fit, then the pose of its F).
  * Replaces: Fit.forward -> E = K^T T^T F T K (train_good_utils.py:356-358) -> utils_F._E_to_M_train (utils_F.py:679-763).
  * Same outputs as dfepe_w8pt_fwd (DFEPE_W8PT_RAW_MATCHES required; DFEPE_W8PT_LOGITS optional; no `save`: forward only) followed
- * by dfepe_cheirality(F_out, pre, ...), bit for bit; for 128 < N <= 2048 below 3072 pairs it is ONE launch (the cooperative
- * workgroup of the fit goes on to decompose pre^T F pre and to triangulate its pair), otherwise the two launches.
+ * by dfepe_cheirality(F_out, pre, ...), bit for bit; for 128 < N <= 2048 up to 1280 pairs (where the forward fit of pixel matches
+ * takes the cooperative workgroup: fit_pose_fused, pytorch-deepfepe_amd/csrc/fit_plan.h) it is ONE launch (that workgroup goes on to
+ * decompose pre^T F pre and to triangulate its pair), otherwise the two launches.
  * workspace: NULL or dfepe_cheirality_workspace_bytes(B) bytes, handed to dfepe_cheirality_ex when the two launches run.
  */
 int dfepe_w8pt_pose_fwd(const float *matches, const float *weights, int B, int N, unsigned flags, float image_w, float image_h,

@@ -3,6 +3,7 @@
 // The batch sums of the loss head are combined deterministically (per-workgroup partial sums in fixed row order, then a
 // one-workgroup kernel that adds the partials in a fixed order) -- no floating-point atomics.
 #include "dfepe_common.h"
+#include "fit_plan.h"
 #include "loss_tail_body.h"
 #include "loss_head_body.h"
 
@@ -273,11 +274,11 @@ extern "C" int dfepe_loss_tail(const float* F_layers, int L, int B, const float*
   H.packed = packed; H.scalars = scalars; H.balance_F = balance_F; H.balance_q = balance_q; H.balance_t = balance_t;
   H.inv_BM = 1.0 / ((double)B * (double)M); H.inv_BML = H.inv_BM / (double)L; H.inv_BL = 1.0 / ((double)B * (double)L);
   const int wd = defer_head ? 1 : 0;
-  if (M <= 16) hipLaunchKernelGGL((loss_tail_kernel<1>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, partials, H, wd);
-  else if (M <= 32) hipLaunchKernelGGL((loss_tail_kernel<2>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, partials, H, wd);
-  else if (M <= 64) hipLaunchKernelGGL((loss_tail_kernel<4>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, partials, H, wd);
-  else if (M <= 112) hipLaunchKernelGGL((loss_tail_kernel<7>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, partials, H, wd);
-  else hipLaunchKernelGGL((loss_tail_kernel<8>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, partials, H, wd);
+  // correspondences per lane as in the fit (fit_plan.h); M <= 128 here, so never the re-reading IT = 0
+  const bool launched = with_it_in<1, 2, 4, 7, 8>(fit_it(M), [&](auto it) {
+    hipLaunchKernelGGL((loss_tail_kernel<it.value>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, partials, H, wd);
+  });
+  if (!launched) return DFEPE_ERR_UNSUPPORTED;
   if (defer_head) return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;  // the first backward fit runs the head
   hipLaunchKernelGGL(loss_tail_head_kernel, dim3(1), dim3(192), 0, st, H);
   return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
@@ -306,12 +307,10 @@ extern "C" int dfepe_loss_tail_jac(const float* F_layers, int L, int B, const fl
   const dim3 grid((B + kPairsPerBlock - 1) / kPairsPerBlock), block(256 + 64 * ((kPairsPerBlock * L + 63) / 64));
   hipStream_t st = static_cast<hipStream_t>(stream);
   TailHead H = {};
-#define DFEPE_TAIL_JAC(IT_) hipLaunchKernelGGL((loss_tail_kernel<IT_, true>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, nullptr, H, 0)
-  if (M <= 16) DFEPE_TAIL_JAC(1);
-  else if (M <= 32) DFEPE_TAIL_JAC(2);
-  else if (M <= 64) DFEPE_TAIL_JAC(4);
-  else DFEPE_TAIL_JAC(7);
-#undef DFEPE_TAIL_JAC
+  const bool launched = with_it_in<1, 2, 4, 7>(fit_it(M), [&](auto it) {  // 8 per lane was rejected above
+    hipLaunchKernelGGL((loss_tail_kernel<it.value, true>), grid, block, 0, st, A.F_layers, A.L, A.B, A.M, A.t_stride, A.T1, A.T2, A.K, A.virt1, A, nullptr, H, 0);
+  });
+  if (!launched) return DFEPE_ERR_UNSUPPORTED;
   return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
 }
 

@@ -69,6 +69,22 @@ struct W8Args {
   bool row_per_pair;  // host side only: never the cooperative workgroup (DFEPE_W8PT_ROW_PER_PAIR)
 };
 
+// host side: the (validated) arguments of dfepe_w8pt_fwd as the kernels take them
+inline W8Args w8_args_of(const float* pts1, const float* pts2, const float* weights, int B, int N, int n_weight_sets, unsigned flags,
+                         float image_w, float image_h, float clamp_at, float* F_out, float* residual, float* epi_res, float* save,
+                         float* weights_out) {
+  const bool raw = (flags & DFEPE_W8PT_RAW_MATCHES) != 0;
+  W8Args A;
+  A.pts1 = pts1; A.pts2 = pts2; A.wts = weights;
+  A.Bm = B; A.B = B * n_weight_sets; A.N = N;
+  A.hw_sx = raw ? 2.0f / image_w : 0.f; A.hw_sy = raw ? 2.0f / image_h : 0.f; A.clamp_at = clamp_at;
+  A.F_out = F_out; A.residual = residual; A.epi_res = epi_res; A.save = save; A.weights_out = weights_out;
+  A.logits_mode = (flags & DFEPE_W8PT_LOGITS) ? 1 : 0;
+  A.variant = flags & (DFEPE_W8PT_SQRT2 | DFEPE_W8PT_NO_ROWNORM | DFEPE_W8PT_FORCE_110 | DFEPE_W8PT_NO_HARTLEY);
+  A.row_per_pair = (flags & DFEPE_W8PT_ROW_PER_PAIR) != 0;
+  return A;
+}
+
 // phase markers for scripts/isa_phases.py (hipcc -DDFEPE_ISA_MARKS -S): comments in the assembly, nothing otherwise;
 // -DDFEPE_PHASE_CLOCKS (scripts/ubench/fit_phases.hip only): lane 0 of every wavefront stamps the shader clock at each marker
 #if defined(DFEPE_ISA_MARKS)

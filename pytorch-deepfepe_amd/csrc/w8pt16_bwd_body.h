@@ -38,6 +38,25 @@ struct W8BwdArgs {
   bool row_per_pair;         // host side only: never the cooperative workgroup (DFEPE_W8PT_ROW_PER_PAIR)
 };
 
+// host side: the (validated) arguments of dfepe_w8pt_bwd as the kernels take them
+inline W8BwdArgs w8_bwd_args_of(const float* pts1, const float* pts2, const float* weights, int B, int N, int n_weight_sets, unsigned flags,
+                                float image_w, float image_h, float clamp_at, const float* save, const float* F_out, const float* g_F,
+                                const float* g_residual, const float* g_epi, const float* g_weights_extra, const float* g_scale,
+                                float* g_weights, float* g_pts1, float* g_pts2, const void* pending_loss_head) {
+  const bool raw = (flags & DFEPE_W8PT_RAW_MATCHES) != 0;
+  W8BwdArgs A;
+  A.pts1 = pts1; A.pts2 = pts2; A.wts = weights;
+  A.Bm = B; A.B = B * n_weight_sets; A.N = N;
+  A.hw_sx = raw ? 2.0f / image_w : 0.f; A.hw_sy = raw ? 2.0f / image_h : 0.f; A.clamp_at = clamp_at;
+  A.save = save; A.F_out = F_out; A.g_F = g_F; A.g_res = g_residual; A.g_epi = g_epi; A.g_w_extra = g_weights_extra; A.g_scale = g_scale;
+  A.g_w = g_weights; A.g_p1 = g_pts1; A.g_p2 = g_pts2;
+  A.logits_mode = (flags & DFEPE_W8PT_LOGITS) ? 1 : 0;
+  A.variant = flags & DFEPE_W8PT_NO_ROWNORM;  // the one variant with an adjoint (row kernels, weight gradients)
+  A.pending_head = pending_loss_head;
+  A.row_per_pair = (flags & DFEPE_W8PT_ROW_PER_PAIR) != 0;
+  return A;
+}
+
 __device__ __forceinline__ double guard_den16(double d) {
   // keep the sign, floor the magnitude: repeated eigen/singular values give a large-but-finite gradient, never NaN
   const double lim = 1e-30;

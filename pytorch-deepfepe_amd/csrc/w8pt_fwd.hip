@@ -14,7 +14,6 @@ extern "C" int dfepe_w8pt_fwd(const float* pts1, const float* pts2, const float*
                               int n_weight_sets, unsigned flags, float image_w, float image_h, float clamp_at, float* F_out,
                               float* residual, float* epi_res, float* save, float* weights_out, void* stream) {
   const bool raw = (flags & DFEPE_W8PT_RAW_MATCHES) != 0;
-  const int logits_mode = (flags & DFEPE_W8PT_LOGITS) ? 1 : 0;
   const unsigned variant = flags & (DFEPE_W8PT_SQRT2 | DFEPE_W8PT_NO_ROWNORM | DFEPE_W8PT_FORCE_110 | DFEPE_W8PT_NO_HARTLEY);
   if (B < 0 || N <= 0 || n_weight_sets < 1) return DFEPE_ERR_INVALID_ARG;
   // the textbook variants are forward-only; un-normalised rows alone (Fit(normalize_SVD=False)) have a backward
@@ -26,13 +25,7 @@ extern "C" int dfepe_w8pt_fwd(const float* pts1, const float* pts2, const float*
   if (reinterpret_cast<uintptr_t>(save) & 15u) return DFEPE_ERR_INVALID_ARG;          // wide stores of the record
 
   if (flags & ~DFEPE_W8PT_ALL_FLAGS) return DFEPE_ERR_INVALID_ARG;  // unknown flag bits are rejected, not ignored
-  {
-    W8Args A;
-    A.pts1 = pts1; A.pts2 = pts2; A.wts = weights;
-    A.Bm = B; A.B = B * n_weight_sets; A.N = N;
-    A.hw_sx = raw ? 2.0f / image_w : 0.f; A.hw_sy = raw ? 2.0f / image_h : 0.f; A.clamp_at = clamp_at;
-    A.F_out = F_out; A.residual = residual; A.epi_res = epi_res; A.save = save; A.weights_out = weights_out;
-    A.logits_mode = logits_mode; A.variant = variant; A.row_per_pair = (flags & DFEPE_W8PT_ROW_PER_PAIR) != 0;
-    return dfepe_w8pt16_fwd_launch(A, raw, static_cast<hipStream_t>(stream));
-  }
+  const W8Args A = w8_args_of(pts1, pts2, weights, B, N, n_weight_sets, flags, image_w, image_h, clamp_at, F_out, residual, epi_res, save,
+                              weights_out);
+  return dfepe_w8pt16_fwd_launch(A, raw, static_cast<hipStream_t>(stream));
 }

@@ -907,7 +907,8 @@ def fit_pose(matches: Tensor, weights: Tensor, K: Tensor, image_w: float, image_
              pre: Optional[Tensor] = None, clamp_at: float = 0.5, want_epi: bool = True, logits: bool = False, row_per_pair: bool = False):
     """One weighted 8-point fit and the cheirality-checked pose of its F (BASELINE config 5): w8pt_forward followed by
     cheirality(F, K, matches, depth_thres, pre=pre), same numbers, ONE launch when a cooperative workgroup serves the pair
-    (128 < N <= 2048 below 3072 pairs).  Returns (F, residual, epi | None, weights_out | None, Rt_cam, winner, counts)."""
+    (128 < N <= 2048 up to 1280 pairs: the forward fit's rule for pixel matches, csrc/fit_plan.h; the backward fit keeps the
+    cooperative workgroup up to 3072 pairs).  Returns (F, residual, epi | None, weights_out | None, Rt_cam, winner, counts)."""
     m, w, K = _prep(matches, "matches"), _prep(weights, "weights"), _prep(K, "K")
     pre = None if pre is None else _prep(pre, "pre")
     _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)

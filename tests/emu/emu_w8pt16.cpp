@@ -10,6 +10,7 @@
 #include "w8pt16_body.h"
 #include "w8pt16_bwd_body.h"
 #include "loss_tail_body.h"
+#include "fit_plan.h"
 
 thread_local emu::Row* emu::g_row = nullptr;
 
@@ -53,22 +54,15 @@ void run_row(const std::function<void()>& body) {
   emu::g_row = nullptr;
 }
 
+// every pair on one row, with the correspondences per lane the library's row kernels take (fit_plan.h)
 template <template <int, bool> class Body, class Args>
-int dispatch(const Args& A, int B, int N, bool raw) {
-  for (int pair = 0; pair < B; ++pair) {
+int dispatch(const Args& A, bool raw) {
+  for (int pair = 0; pair < A.B; ++pair) {
     double xch[48];
-    auto go = [&](auto itc, auto rawc) {
-      run_row([&]() { Body<decltype(itc)::value, decltype(rawc)::value>::run(A, pair, xch); });
-    };
-    auto with_it = [&](auto rawc) {
-      if (N > 128) go(std::integral_constant<int, 0>{}, rawc);
-      else if (N <= 16) go(std::integral_constant<int, 1>{}, rawc);
-      else if (N <= 32) go(std::integral_constant<int, 2>{}, rawc);
-      else if (N <= 64) go(std::integral_constant<int, 4>{}, rawc);
-      else if (N <= 112) go(std::integral_constant<int, 7>{}, rawc);
-      else go(std::integral_constant<int, 8>{}, rawc);
-    };
-    if (raw) with_it(std::true_type{}); else with_it(std::false_type{});
+    with_it(fit_it(A.N), [&](auto it) {
+      constexpr int IT = decltype(it)::value;
+      run_row([&]() { if (raw) Body<IT, true>::run(A, pair, xch); else Body<IT, false>::run(A, pair, xch); });
+    });
   }
   return 0;
 }
@@ -98,15 +92,9 @@ extern "C" int emu_w8pt16_fwd(const float* pts1, const float* pts2, const float*
                               unsigned flags, float image_w, float image_h, float clamp_at, float* F_out, float* residual,
                               float* epi_res, float* save, float* weights_out) {
   if (N < 1) return -3;
-  const bool raw = (flags & DFEPE_W8PT_RAW_MATCHES) != 0;
-  W8Args A;
-  A.pts1 = pts1; A.pts2 = pts2; A.wts = weights;
-  A.Bm = B; A.B = B * n_weight_sets; A.N = N;
-  A.hw_sx = raw ? 2.0f / image_w : 0.f; A.hw_sy = raw ? 2.0f / image_h : 0.f; A.clamp_at = clamp_at;
-  A.F_out = F_out; A.residual = residual; A.epi_res = epi_res; A.save = save; A.weights_out = weights_out;
-  A.logits_mode = (flags & DFEPE_W8PT_LOGITS) ? 1 : 0;
-  A.variant = flags & (DFEPE_W8PT_SQRT2 | DFEPE_W8PT_NO_ROWNORM | DFEPE_W8PT_FORCE_110 | DFEPE_W8PT_NO_HARTLEY);
-  return dispatch<FwdBody>(A, A.B, N, raw);
+  const W8Args A = w8_args_of(pts1, pts2, weights, B, N, n_weight_sets, flags, image_w, image_h, clamp_at, F_out, residual, epi_res, save,
+                              weights_out);
+  return dispatch<FwdBody>(A, (flags & DFEPE_W8PT_RAW_MATCHES) != 0);
 }
 
 extern "C" int emu_w8pt16_bwd(const float* pts1, const float* pts2, const float* weights, int B, int N, int n_weight_sets,
@@ -114,15 +102,9 @@ extern "C" int emu_w8pt16_bwd(const float* pts1, const float* pts2, const float*
                               const float* F_out, const float* g_F, const float* g_residual, const float* g_epi,
                               const float* g_weights_extra, const float* g_scale, float* g_weights, float* g_pts1, float* g_pts2) {
   if (N < 1) return -3;
-  const bool raw = (flags & DFEPE_W8PT_RAW_MATCHES) != 0;
-  W8BwdArgs A;
-  A.pts1 = pts1; A.pts2 = pts2; A.wts = weights;
-  A.Bm = B; A.B = B * n_weight_sets; A.N = N;
-  A.hw_sx = raw ? 2.0f / image_w : 0.f; A.hw_sy = raw ? 2.0f / image_h : 0.f; A.clamp_at = clamp_at;
-  A.save = save; A.F_out = F_out; A.g_F = g_F; A.g_res = g_residual; A.g_epi = g_epi; A.g_w_extra = g_weights_extra; A.g_scale = g_scale;
-  A.g_w = g_weights; A.g_p1 = g_pts1; A.g_p2 = g_pts2;
-  A.logits_mode = (flags & DFEPE_W8PT_LOGITS) ? 1 : 0;
-  return dispatch<BwdBody>(A, A.B, N, raw);
+  const W8BwdArgs A = w8_bwd_args_of(pts1, pts2, weights, B, N, n_weight_sets, flags, image_w, image_h, clamp_at, save, F_out, g_F, g_residual,
+                                     g_epi, g_weights_extra, g_scale, g_weights, g_pts1, g_pts2, nullptr);
+  return dispatch<BwdBody>(A, (flags & DFEPE_W8PT_RAW_MATCHES) != 0);
 }
 
 // the fused loss tail, pair by pair (the batch sums of the loss head are left to the caller: part[B][kTailParts])
@@ -141,12 +123,19 @@ extern "C" int emu_loss_tail(const float* F_layers, int L, int B, const float* T
     float lds[kTailLdsFloats];
     double* pp = part + (size_t)pair * kTailParts;
     for (int e = 0; e < kTailParts; ++e) pp[e] = 0.0;
-    auto go = [&](auto itc) { run_row([&]() { loss_tail_pair<decltype(itc)::value>(A, pair, lds, pp); }); };
-    if (M <= 16) go(std::integral_constant<int, 1>{});
-    else if (M <= 32) go(std::integral_constant<int, 2>{});
-    else if (M <= 64) go(std::integral_constant<int, 4>{});
-    else if (M <= 112) go(std::integral_constant<int, 7>{});
-    else go(std::integral_constant<int, 8>{});
+    with_it_in<1, 2, 4, 7, 8>(fit_it(M), [&](auto it) { run_row([&]() { loss_tail_pair<decltype(it)::value>(A, pair, lds, pp); }); });
   }
   return 0;
+}
+
+// The library's launch plan (fit_plan.h) for the plan-table test -- a hook of this test library, not an entry point of the product.
+// out: kind (0 Row, 1 RowLean, 2 Pair2, 3 Coop), it, up of the forward (backward = 0) or the backward plan; then whether a deferred
+// loss head rides on that backward launch, and whether dfepe_w8pt_pose_fwd is one launch at this shape.
+extern "C" void emu_fit_plan(int backward, int N, int pairs, int raw, int row_per_pair, int pgrad, int plain, int gF_only, int force_lean,
+                             int force_pair2, int forced_launches, int* out) {
+  const FitPlan p = backward ? fit_bwd_plan(N, pairs, row_per_pair != 0, pgrad != 0, plain != 0, gF_only != 0)
+                             : fit_fwd_plan(N, pairs, raw != 0, row_per_pair != 0, force_lean, force_pair2);
+  out[0] = (int)p.kind; out[1] = p.it; out[2] = p.up ? 1 : 0;
+  out[3] = (backward && fit_bwd_head_rides(p, raw != 0)) ? 1 : 0;
+  out[4] = fit_pose_fused(N, pairs, row_per_pair != 0, forced_launches) ? 1 : 0;
 }

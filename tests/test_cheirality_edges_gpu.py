@@ -288,12 +288,14 @@ def test_correspondences_behind_every_candidate(dfepe):
 
 
 # ---- the fused routes -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,N", [(1, 129), (9, 1000), (512, 2048), (3071, 129), (3072, 129), (9, 2049)],
-                         ids=["B1-N129_first_cooperative_N", "B9-N1000", "B512-N2048_last_cooperative_N", "B3071_last_cooperative_B",
-                              "B3072_two_launches", "N2049_two_launches"])
+@pytest.mark.parametrize("B,N", [(1, 129), (9, 1000), (512, 2048), (1280, 129), (1281, 129), (3071, 129), (3072, 129), (9, 2049)],
+                         ids=["B1-N129_first_cooperative_N", "B9-N1000", "B512-N2048_last_cooperative_N", "B1280_last_cooperative_B",
+                              "B1281_two_launches", "B3071_two_launches_below_backward_limit", "B3072_two_launches_at_backward_limit",
+                              "N2049_two_launches"])
 def test_fused_routes(dfepe, B, N):
-    """ops.cheirality(F, pre = T K) and ops.fit_pose (one cooperative launch for 128 < N <= 2048 below 3072 pairs) through the
-    same comparison, the restatement's E formed in fp64 from the fp32 F the device returns."""
+    """ops.cheirality(F, pre = T K) and ops.fit_pose (one cooperative launch for 128 < N <= 2048 up to 1280 pairs, the forward fit's limit
+    for pixel matches; csrc/fit_plan.h.  3072 pairs is the BACKWARD fit's limit: the forward takes the two launches on both sides of it)
+    through the same comparison, the restatement's E formed in fp64 from the fp32 F the device returns."""
     D = min(B, 8)
     sc = dfepe.synth.make_scene(D, N, seed=B + N, outlier_ratio=0.2, noise_px=0.5)
     src = np.random.default_rng(B).permutation(B) % D

@@ -22,7 +22,7 @@ def emu():
     os.makedirs(out, exist_ok=True)
     lib = os.path.join(out, "libemu_w8pt16.so")
     srcs = [os.path.join(EMU_DIR, "emu_w8pt16.cpp"), os.path.join(EMU_DIR, "rowgroup.h")] + [
-        os.path.join(REPO, "pytorch-deepfepe_amd", "csrc", f) for f in ("w8pt16_body.h", "w8pt16_bwd_body.h", "dfepe_math.h")]
+        os.path.join(REPO, "pytorch-deepfepe_amd", "csrc", f) for f in ("w8pt16_body.h", "w8pt16_bwd_body.h", "loss_tail_body.h", "dfepe_math.h", "fit_plan.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in srcs):
         subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", f"-I{EMU_DIR}", f"-I{REPO}/pytorch-deepfepe_amd/csrc",
                         f"-I{REPO}/include", srcs[0], "-o", lib], check=True)
@@ -34,6 +34,8 @@ def emu():
     L.emu_set_lean.argtypes = [I]
     L.emu_w8pt16_bwd.restype = I
     L.emu_w8pt16_bwd.argtypes = [P, P, P, I, I, I, U, F, F, F, P, P, P, P, P, P, P, P, P, P]
+    L.emu_fit_plan.restype = None
+    L.emu_fit_plan.argtypes = [I] * 11 + [ctypes.POINTER(I)]
     return L
 
 
@@ -63,6 +65,106 @@ def emu_bwd(L, pts1, pts2, w, flags, save, F, gF, gRes, gEpi, want_pts=False, cl
                           _p(save), _p(F), _p(gF), _p(gRes), _p(gEpi), None, _p(g_scale), _p(gW), _p(gP1), _p(gP2))
     assert rc == 0
     return gW, gP1, gP2
+
+
+# ---- the launch plan (csrc/fit_plan.h) ------------------------------------------------------------------------------------
+ROW, ROW_LEAN, PAIR2, COOP = 0, 1, 2, 3
+PLAN_N = (1, 16, 17, 32, 33, 64, 65, 112, 113, 128, 129, 512, 513, 1024, 1025, 2048, 2049)
+PLAN_PAIRS = (1, 1280, 1281, 3072, 3073, 8191, 8192, 12287, 12288)
+
+
+def fit_plan(L, backward, N, pairs, raw=1, row_per_pair=0, pgrad=0, plain=1, gF_only=0, force_lean=-1, force_pair2=-1, pose_launches=0):
+    """(kind, it, up, head rides, pose fused) as the library's plan functions answer."""
+    out = (ctypes.c_int * 5)()
+    L.emu_fit_plan(backward, N, pairs, raw, row_per_pair, pgrad, plain, gF_only, force_lean, force_pair2, pose_launches, out)
+    return tuple(out)
+
+
+def _row_it(N):  # correspondences per lane of a row: written out, N <= 16 -> 1, <= 32 -> 2, <= 64 -> 4, <= 112 -> 7, <= 128 -> 8, above -> 0
+    return {1: 1, 16: 1, 17: 2, 32: 2, 33: 4, 64: 4, 65: 7, 112: 7, 113: 8, 128: 8}.get(N, 0)
+
+
+def _coop_it(N):  # of a cooperative workgroup: N <= 512 -> 2, <= 1024 -> 4, else 8
+    return {129: 2, 512: 2, 513: 4, 1024: 4, 1025: 8, 2048: 8}[N]
+
+
+def _expected_fwd(N, pairs, raw, row_per_pair, force_lean=-1, force_pair2=-1):
+    """The forward rule, in its order: cooperative workgroup; two rows per pair; row re-reading its correspondences; row (lean)."""
+    if 128 < N <= 2048 and pairs <= 3072 and not row_per_pair and (pairs <= 1280 or not raw):
+        return COOP, _coop_it(N)
+    pair2 = pairs < 8192 if force_pair2 < 0 else force_pair2 != 0
+    if raw and N > 128 and pair2:
+        return PAIR2, 0
+    if N > 128:
+        return ROW, 0
+    lean = pairs >= 12288 if force_lean < 0 else force_lean != 0
+    return (ROW_LEAN if 64 < N <= 128 and lean else ROW), _row_it(N)
+
+
+def _expected_bwd(N, pairs, row_per_pair, pgrad, plain, gF_only):
+    if not pgrad and plain and 128 < N <= 2048 and pairs <= 3072 and not row_per_pair:
+        return COOP, _coop_it(N), 1
+    return ROW, _row_it(N), 0 if (not pgrad and plain and gF_only) else 1
+
+
+@pytest.mark.parametrize("row_per_pair", [0, 1])
+@pytest.mark.parametrize("raw", [1, 0])
+def test_fit_plan_forward_at_every_edge(emu, raw, row_per_pair):
+    """Which kernel the forward fit launches, and with how many correspondences per lane, on either side of every edge of the rule
+    (fit_plan.h); the expectation is the rule written out above, not a second call of the code.  dfepe_w8pt_pose_fwd is one launch
+    exactly where pixel matches get the cooperative workgroup."""
+    for N in PLAN_N:
+        for pairs in PLAN_PAIRS:
+            got = fit_plan(emu, 0, N, pairs, raw=raw, row_per_pair=row_per_pair)
+            assert got[:2] == _expected_fwd(N, pairs, raw, row_per_pair), (N, pairs, got)
+            fused = 128 < N <= 2048 and pairs <= 1280 and not row_per_pair
+            assert got[4] == int(fused), (N, pairs, got)
+            assert fit_plan(emu, 0, N, pairs, raw=raw, row_per_pair=row_per_pair, pose_launches=1)[4] == int(fused)
+            assert fit_plan(emu, 0, N, pairs, raw=raw, row_per_pair=row_per_pair, pose_launches=2)[4] == 0
+    # spot values, spelled out: the benchmark's shapes and the edge round 5 moved
+    assert fit_plan(emu, 0, 100, 4096)[:2] == (ROW, 7) and fit_plan(emu, 0, 100, 32768)[:2] == (ROW_LEAN, 7)
+    assert fit_plan(emu, 0, 1000, 4096)[:2] == (PAIR2, 0) and fit_plan(emu, 0, 1000, 4096, raw=0)[:2] == (ROW, 0)
+    assert fit_plan(emu, 0, 129, 1280)[:2] == (COOP, 2) and fit_plan(emu, 0, 129, 1281)[:2] == (PAIR2, 0)
+    assert fit_plan(emu, 0, 129, 3072, raw=0)[:2] == (COOP, 2) and fit_plan(emu, 0, 129, 3073, raw=0)[:2] == (ROW, 0)
+
+
+@pytest.mark.parametrize("force_lean,force_pair2", [(0, -1), (1, -1), (-1, 0), (-1, 1), (1, 1), (0, 0)])
+def test_fit_plan_forward_forced_switches(emu, force_lean, force_pair2):
+    """DFEPE_FIT_LEAN / DFEPE_FIT_PAIR2 (0 / 1) replace the pair-count conditions of the lean and the two-row kernel and nothing else."""
+    for N in PLAN_N:
+        for pairs in PLAN_PAIRS:
+            for raw in (1, 0):
+                got = fit_plan(emu, 0, N, pairs, raw=raw, force_lean=force_lean, force_pair2=force_pair2)
+                assert got[:2] == _expected_fwd(N, pairs, raw, 0, force_lean, force_pair2), (N, pairs, raw, got)
+    if force_lean == 1:
+        assert fit_plan(emu, 0, 65, 1, force_lean=1)[:2] == (ROW_LEAN, 7) and fit_plan(emu, 0, 64, 12288, force_lean=1)[:2] == (ROW, 4)
+    if force_lean == 0:
+        assert fit_plan(emu, 0, 128, 12288, force_lean=0)[:2] == (ROW, 8)
+    if force_pair2 == 1:
+        assert fit_plan(emu, 0, 2049, 12288, force_pair2=1)[:2] == (PAIR2, 0) and fit_plan(emu, 0, 2049, 1, raw=0, force_pair2=1)[:2] == (ROW, 0)
+    if force_pair2 == 0:
+        assert fit_plan(emu, 0, 129, 1281, force_pair2=0)[:2] == (ROW, 0) and fit_plan(emu, 0, 129, 1280, force_pair2=0)[:2] == (COOP, 2)
+
+
+@pytest.mark.parametrize("pgrad,plain,gF_only", [(0, 1, 0), (0, 1, 1), (1, 1, 0), (1, 1, 1), (0, 0, 0), (0, 0, 1)])
+def test_fit_plan_backward_at_every_edge(emu, pgrad, plain, gF_only):
+    """The backward: the cooperative workgroup up to 3072 pairs (its own limit, not the forward's 1280) without point gradients or
+    variant flags, rows otherwise; the instantiation without pass A when g_F is the only gradient; the deferred loss head rides
+    only on that one, for pixel matches."""
+    for N in PLAN_N:
+        for pairs in PLAN_PAIRS:
+            for row_per_pair in (0, 1):
+                exp = _expected_bwd(N, pairs, row_per_pair, pgrad, plain, gF_only)
+                for raw in (1, 0):
+                    got = fit_plan(emu, 1, N, pairs, raw=raw, row_per_pair=row_per_pair, pgrad=pgrad, plain=plain, gF_only=gF_only)
+                    assert got[:3] == exp, (N, pairs, row_per_pair, got)
+                    rides = raw and not pgrad and plain and gF_only and exp[0] == ROW
+                    assert got[3] == int(bool(rides)), (N, pairs, row_per_pair, raw, got)
+    if (pgrad, plain, gF_only) == (0, 1, 1):
+        assert fit_plan(emu, 1, 100, 4096, gF_only=1) == (ROW, 7, 0, 1, 0)     # the captured step of the benchmark
+        assert fit_plan(emu, 1, 129, 1281, gF_only=1)[:4] == (COOP, 2, 1, 0)   # past the forward's limit, inside the backward's
+        assert fit_plan(emu, 1, 129, 3072, gF_only=1)[:4] == (COOP, 2, 1, 0)
+        assert fit_plan(emu, 1, 129, 3073, gF_only=1)[:4] == (ROW, 0, 0, 1)
 
 
 def unit_align(a, ref):

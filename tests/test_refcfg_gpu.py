@@ -5,7 +5,8 @@ and pose loss, every output and every parameter gradient.  GPU box only.
 At this shape the package runs kernels its N = 100 golden test never reaches: the split-K estimator products with the register-resident
 normalisation and adjoint (dfepe_est_norm_fwd_r / dfepe_est_in_bwd_r), update_weights four times on one parameter preparation, and the
 cooperative 4-wavefront workgroup per pair in the fit.  Nothing in the ABI reports which fit kernel ran: the cooperative route follows
-from the rule in include/dfepe.h (128 < N <= 2048 below 3072 pairs) for every fit of the default step here; the same step is run a second
+from the rule in csrc/fit_plan.h (128 < N <= 2048; forward fit of pixel matches up to 1280 pairs, backward fit up to 3072) for every fit
+of the default step here; the same step is run a second
 time with DFEPE_W8PT_ROW_PER_PAIR on every fit (one 16-lane row per pair), and BOTH routes are held to the fixture.
 
 Yardstick: every compared quantity sits within max(4 x ref32_dist, floor) of the float64 truth, where ref32_dist is the distance of the
