@@ -647,6 +647,49 @@ int dfepe_ransac_fundamental(const float *matches, int B, int N, double threshol
 int dfepe_ransac_in_front(const float *E, const float *K, const float *matches, int B, int N, float depth_thres, const int *winner,
                           unsigned char *mask, void *stream);
 
+/*
+ * Robust essential matrix of every pair by the five-point algorithm: OpenCV 3.4 findEssentialMat(x1, x2, focal, pp, RANSAC,
+ * confidence, threshold), batched, in everything but the random stream.  Replaces: cv2.findEssentialMat in
+ * utils_opencv.recover_camera_opencv(five_point=True) (deepFEPE/dsac_tools/utils_opencv.py:147-151), the `opencv_5p` baseline of
+ * val_rt (train_good_utils.py:615-633).  The pose that follows (cv2.recoverPose, :177) is dfepe_cheirality_ex on E_out itself
+ * and masked_matches, with the same K, and dfepe_ransac_in_front.
+ *   matches [B,N,4] fp32 pixels (x1, y1, x2, y2), 16-byte aligned; K [B,9] fp32 row-major (K00, K11 the focal lengths, K02, K12
+ *     the principal point; nothing else of K is read).  6 <= N <= 4096 (N < 6: DFEPE_ERR_UNSUPPORTED -- with N = 5 OpenCV returns
+ *     the stacked models of the one sample, which is not built; N > 4096: the pair does not fit in LDS); B <= 65535 (else
+ *     UNSUPPORTED); threshold >= 0 (pixels), confidence p in [0, 1], max_iters >= 1 (else INVALID_ARG); a NULL required pointer
+ *     is INVALID_ARG; B == 0 returns 0 before any launch.
+ *   workspace  dfepe_ransac5_workspace_bytes(B, N, max_iters) bytes of device memory, 16-byte aligned, overwritten
+ *   E_out [B,9] fp32 (the winner, the fp32 rounding of its hyp_E entry; zeros when the pair has no model); inlier_mask [B,N]
+ *   uint8; n_inliers [B] int32 (0: no model); iters_run [B] int32 (iterations consumed); best_hyp [B,2] int32 (winning
+ *   iteration and root, -1 -1 without a model; may be NULL); hyp_counts [B,max_iters,10] int32 or NULL: the count table
+ *   (inliers of root r of iteration k; -1 = no such root; with NULL the table lives in the workspace); hyp_E
+ *   [B,max_iters,10,9] fp64 or NULL: the hypotheses themselves, unused slots zero; masked_matches [B,N,4] or NULL: the matches
+ *   with every non-inlier row set to quiet NaN.
+ * The algorithm (sequential definition; the device evaluates all max_iters iterations in parallel and applies the rule of step
+ * 4 to the counts, with the same result):
+ *   0 Normalised coordinates in fp64, q = ((x - K02) / K00, (y - K12) / K11) for both images, and the threshold in the same
+ *     units, t = threshold / ((K00 + K11) / 2).  With the identity for K the points and the threshold are used as given.
+ *   1 Sampling.  The stream of dfepe_ransac_fundamental (same key_k, same Lemire map, independent of the pair); 5 distinct
+ *     indices, no geometric rejection: every iteration has a sample, and the table code -2 is never written.
+ *   2 Five-point solve in fp64: null space {X, Y, Z, W} of the 5x9 system with rows [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1,
+ *     1] (so that q2^T E q1 = 0 with E row-major; Householder QR), E = x X + y Y + z Z + W, and all real solutions (at most 10)
+ *     of det E = 0 and 2 E E^T E - tr(E E^T) E = 0.  Nister's route: the ten cubics as a 10x20 matrix, Gauss-Jordan
+ *     elimination with row pivoting, the real roots of the degree-10 determinant in z isolated between the roots of its
+ *     derivatives, (x, y) from the null vector, four Gauss-Newton steps on (x, y, z) against the ten constraints.  Each E is
+ *     scaled to unit Frobenius norm with its entry of largest magnitude positive; a candidate whose constraints then exceed 1e-9
+ *     is not a solution and is dropped.  The solutions of an iteration are in ascending z: a function of the sample alone.
+ *   3 Score: a correspondence is an inlier iff (q2^T E q1)^2 <= t^2 ((E q1)_0^2 + (E q1)_1^2 + (E^T q2)_0^2 + (E^T q2)_1^2), the
+ *     Sampson error of OpenCV's EMEstimatorCallback::computeError, evaluated in fp64 without divisions.  Decisions can differ
+ *     from an exact evaluation only inside a relative band of 1e-6 around t^2.
+ *   4 Select: the rule of dfepe_ransac_fundamental with 10 slots per iteration: a model whose count exceeds max(best, 4) becomes
+ *     the best, and niters = RANSACUpdateNumIters(p, (N - count) / N, 5, niters) (den = 1 - (1 - ep)^5).
+ */
+size_t dfepe_ransac5_workspace_bytes(int B, int N, int max_iters);
+int dfepe_ransac_essential(const float *matches, const float *K, int B, int N, double threshold, double confidence,
+                           int max_iters, unsigned long long seed, void *workspace, float *E_out,
+                           unsigned char *inlier_mask, int *n_inliers, int *iters_run, int *best_hyp,
+                           int *hyp_counts, double *hyp_E, float *masked_matches, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ TAIL_MAX_LAYERS = 16  # dfepe_loss_tail: layers per launch (kTailMaxLayers, csrc
 EPI_HOMOGENEOUS = 8
 CHEIR_FP64_ONLY = 1
 RANSAC_MIN_N = 15  # dfepe_ransac_fundamental: below, OpenCV switches to LMedS (not built)
+RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked models of the one sample (not built)
 
 _P = c_void_p
 _SIGNATURES = {
@@ -102,6 +103,8 @@ _SIGNATURES = {
     "dfepe_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_ransac_fundamental": (c_int, [_P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_ransac_in_front": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
+    "dfepe_ransac5_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_ransac_essential": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

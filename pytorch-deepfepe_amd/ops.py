@@ -1002,6 +1002,61 @@ def ransac_pose(matches: Tensor, K: Tensor, threshold: float = 0.1, confidence: 
     return out
 
 
+def ransac_essential(matches: Tensor, K: Tensor, threshold: float = 1.0, confidence: float = 0.999, max_iters: int = 1000, seed: int = 0,
+                     want_hyp_counts: bool = False, want_hyp_E: bool = False, want_masked: bool = False):
+    """matches [B,N,4] pixels, K [B,3,3] -> robust E of every pair by OpenCV 3.4's findEssentialMat(RANSAC) algorithm, the
+    five-point baseline (utils_opencv.py:147-151; include/dfepe.h spells out the normalisation, the sampler, the five-point solve,
+    the Sampson score and the stopping rule).  The defaults are cv2's own for findEssentialMat.
+    Returns dict(E [B,3,3] (unit Frobenius norm, largest entry positive; zeros without a model), mask [B,N] uint8, n_inliers [B],
+    iters_run [B], best_hyp [B,2] (iteration, root; -1 without a model), hyp_counts [B,max_iters,10] | None (-1: no root), hyp_E
+    [B,max_iters,10,3,3] float64 | None (the hypotheses; unused slots zero), masked [B,N,4] | None (non-inlier rows NaN)).
+    No host synchronisation.  6 <= N <= 4096."""
+    m, K = _prep(matches, "matches"), _prep(K, "K")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    B, N = m.shape[0], m.shape[1]
+    _shape(K, "K (one intrinsic matrix per pair)", B, 3, 3)
+    if N < _lib.RANSAC5_MIN_N:
+        raise _lib.DfepeError(f"ransac_essential: {N} correspondences per pair; the five-point RANSAC estimator needs at least "
+                              f"{_lib.RANSAC5_MIN_N}")
+    L = _lib.lib()
+    dev = m.device
+    T = int(max_iters)
+    ws = torch.empty(max(1, (int(L.dfepe_ransac5_workspace_bytes(B, N, T)) + 15) // 16), 2, dtype=torch.float64, device=dev)
+    out = {
+        "E": torch.empty(B, 3, 3, device=dev),
+        "mask": torch.empty(B, N, device=dev, dtype=torch.uint8),
+        "n_inliers": torch.empty(B, device=dev, dtype=torch.int32),
+        "iters_run": torch.empty(B, device=dev, dtype=torch.int32),
+        "best_hyp": torch.empty(B, 2, device=dev, dtype=torch.int32),
+        "hyp_counts": torch.empty(B, T, 10, device=dev, dtype=torch.int32) if want_hyp_counts else None,
+        "hyp_E": torch.empty(B, T, 10, 3, 3, device=dev, dtype=torch.float64) if want_hyp_E else None,
+        "masked": torch.empty(B, N, 4, device=dev) if want_masked else None,
+    }
+    with _on(dev):
+        rc = L.dfepe_ransac_essential(_ptr(m), _ptr(K), B, N, float(threshold), float(confidence), T, int(seed) & ((1 << 64) - 1),
+                                      _ptr(ws), _ptr(out["E"]), _ptr(out["mask"]), _ptr(out["n_inliers"]), _ptr(out["iters_run"]),
+                                      _ptr(out["best_hyp"]), _ptr(out["hyp_counts"]), _ptr(out["hyp_E"]), _ptr(out["masked"]), _stream())
+    _lib.check(rc, "dfepe_ransac_essential")
+    return out
+
+
+def ransac_essential_pose(matches: Tensor, K: Tensor, threshold: float = 1.0, confidence: float = 0.999, max_iters: int = 1000,
+                          seed: int = 0, depth_thres: float = 50.0):
+    """The five-point baseline of utils_opencv.recover_camera_opencv(five_point=True) (utils_opencv.py:147-151,177) for every
+    pair: ransac_essential with the camera recover_pose_camera(K) -- the reference gives findEssentialMat and recoverPose the same
+    focal length and principal point -- then cv2.recoverPose(E, x1, x2, that camera, mask=inliers): E goes to the unchanged
+    cheirality kernel as it is (no K^T F K, no projection), on the matches with the non-inlier rows set to NaN.
+    Returns the ransac_essential dict with Rt_cam [B,3,4], winner [B], counts [B,4] and in_front [B,N] uint8 added."""
+    K = _prep(K, "K")
+    Kp = torch.zeros_like(K)  # compat.utils_opencv.recover_pose_camera: focal K00, principal point (K02, K12)
+    Kp[:, 0, 0] = Kp[:, 1, 1] = K[:, 0, 0]
+    Kp[:, 0, 2], Kp[:, 1, 2], Kp[:, 2, 2] = K[:, 0, 2], K[:, 1, 2], 1.0
+    out = ransac_essential(matches, Kp, threshold, confidence, max_iters, seed, want_masked=True)
+    Rt, win, cnt = cheirality(out["E"], Kp, out["masked"], depth_thres)
+    out.update({"Rt_cam": Rt, "winner": win, "counts": cnt, "in_front": ransac_in_front(out["E"], Kp, out["masked"], win, depth_thres)})
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # validation summary reductions ("next" row f-2)
 # ------------------------------------------------------------------------------------------------
