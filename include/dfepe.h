@@ -690,6 +690,35 @@ int dfepe_ransac_essential(const float *matches, const float *K, int B, int N, d
                            unsigned char *inlier_mask, int *n_inliers, int *iters_run, int *best_hyp,
                            int *hyp_counts, double *hyp_E, float *masked_matches, void *stream);
 
+/*
+ * Optimal correction of correspondences onto a given epipolar geometry (Hartley & Sturm), batched: for every pair (p, q) the pair
+ * (p', q') with q'^T F p' = 0 exactly that minimises |p - p'|^2 + |q - q'|^2 -- cv2.correctMatches(F, p, q), OpenCV's argument
+ * order.  Replaces: the cv2.correctMatches call of get_virt_x1x2_np / get_virt_x1x2 (deepFEPE/dsac_tools/utils_misc.py:176,206),
+ * which makes the virtual points pts*_virt_ori of the F-loss once per sample on the host.
+ *   stream comes first here (a hipStream_t, as everywhere).
+ *   F [B,9] fp64 row-major with f_stride = 9, or one F [9] for all pairs with f_stride = 0 (any other stride: INVALID_ARG).
+ *     F is fp64 because its rounding to fp32 moves the result by more than one fp32 spacing at pixel scale.
+ *   p, q [B,M,2] fp32 pixels; p_out, q_out [B,M,2] fp32; cost [B,M] fp32 or NULL: the minimal |p - p'|^2 + |q - q'|^2 in px^2.
+ *   B < 0, M < 0: INVALID_ARG; B == 0 or M == 0 returns 0 before any launch; then a NULL required pointer is INVALID_ARG; more
+ *   than 2^31 - 1 workgroups of 256 points: UNSUPPORTED.
+ * One lane per point, everything in fp64:
+ *   1 the epipoles e1 (F e1 = 0), e2 (e2^T F = 0): the largest cross product of two rows / two columns of F (scaled by max |F|);
+ *   2 p and q are translated to the origins, the translated epipoles scaled to ex^2 + ey^2 = 1 and rotated onto (1, 0, f1),
+ *     (1, 0, f2); of the transformed F only a = G11, b = G12, c = G21, d = G22 remain;
+ *   3 the real roots of the sextic t ((a t + b)^2 + f2^2 (c t + d)^2)^2 - (a d - b c) (1 + f1^2 t^2)^2 (a t + b) (c t + d)
+ *     (Hartley & Zisserman eq. 12.7; coefficients divided by the largest), those with |t| <= 1 in t and those with |t| >= 1 in
+ *     u = 1 / t: in either chart the roots in [-1, 1] are bracketed by the roots of the derivative, level by level from the linear
+ *     fifth derivative, and every bracket with a sign change gets 36 halvings and 3 Newton steps;
+ *   4 the cost s(t) = t^2 / (1 + f1^2 t^2) + (c t + d)^2 / ((a t + b)^2 + f2^2 (c t + d)^2) at every root and at t = infinity; the
+ *     smallest wins, its closest points (t^2 f1, t, t^2 f1^2 + 1) and (f2 (c t + d)^2, -(a t + b)(c t + d), f2^2 (c t + d)^2 +
+ *     (a t + b)^2) are rotated and translated back and rounded to fp32.
+ *   A point on an epipole (ex^2 + ey^2 = 0) and any lane whose result is not finite get quiet NaN in all five outputs, as OpenCV
+ *   returns NaN there.
+ * dfepe_version() stays 154 with this addition: the number is pinned by existing tests, and nothing that existed changes.
+ */
+int dfepe_correct_matches(void *stream, const double *F, long f_stride, const float *p, const float *q, int B, int M, float *p_out,
+                          float *q_out, float *cost);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,7 @@ _SIGNATURES = {
     "dfepe_ransac_in_front": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
     "dfepe_ransac5_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_ransac_essential": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfepe_correct_matches": (c_int, [_P, _P, c_long, _P, _P, c_int, c_int, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

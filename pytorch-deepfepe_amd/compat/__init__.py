@@ -7,7 +7,8 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.dsac_tools.utils_F         ->   compat.utils_F
     deepFEPE.dsac_tools.utils_geo       ->   compat.utils_geo
     deepFEPE.train_good_utils           ->   compat.train_good_utils (get_all_loss_DeepF, get_Rt_loss, get_matches_from_SP)
-    deepFEPE.dsac_tools.utils_misc      ->   compat.utils_misc      (homogeneous / rigid-transform helpers, crop_or_pad_choice)
+    deepFEPE.dsac_tools.utils_misc      ->   compat.utils_misc      (homogeneous / rigid-transform helpers, crop_or_pad_choice,
+                                                                    get_virt_x1x2*: the F-loss's virtual points, no cv2)
     deepFEPE.dsac_tools.utils_opencv    ->   compat.utils_opencv    (recover_camera_opencv: the 8-point RANSAC baseline, no cv2)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)

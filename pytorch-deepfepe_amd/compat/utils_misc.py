@@ -1,8 +1,12 @@
 """Mirror of the helpers of deepFEPE/dsac_tools/utils_misc.py that the hot path and its callers use: homogeneous-coordinate
 helpers, the cross-product matrix, rigid-transform inversion / padding and the crop-or-pad index draw.  These are tiny
-host-side or elementwise operations (no kernel needed); signatures and numerics follow the reference."""
+host-side or elementwise operations (no kernel needed); signatures and numerics follow the reference.  The virtual-point
+generator at the end (get_virt_x1x2_grid / _np / get_virt_x1x2, and get_virt_x1x2_batch for a whole batch on the device) is the
+exception: its cv2.correctMatches is ops.correct_matches, one launch of a HIP kernel."""
 import numpy as np
 import torch
+
+from .. import ops
 
 
 def identity_Rt(dtype=np.float32):
@@ -93,3 +97,83 @@ def crop_or_pad_choice(in_num_points, out_num_points, shuffle=False):
         return choice[:out_num_points]
     pad = np.random.choice(choice, out_num_points - in_num_points, replace=True)
     return np.concatenate([choice, pad])
+
+
+def get_virt_x1x2_grid(im_shape):
+    """The 10 x 10 grid of pixel positions, the same in both images, as float32 [100,2] (utils_misc.py:163-171, line for line)."""
+    step = 0.1
+    sz1 = im_shape
+    sz2 = im_shape
+    xx, yy = np.meshgrid(np.arange(0, 1, step), np.arange(0, 1, step))
+    pts1_virt_b = np.float32(np.vstack((sz1[1] * xx.flatten(), sz1[0] * yy.flatten())).T)
+    pts2_virt_b = np.float32(np.vstack((sz2[1] * xx.flatten(), sz2[0] * yy.flatten())).T)
+    return pts1_virt_b, pts2_virt_b
+
+
+def _correct_matches_np(F_gt, first, second):
+    """cv2.correctMatches(F_gt, first[None], second[None]) for numpy input: one launch on the current GPU, float32 [1,M,2] back."""
+    dev = torch.device("cuda")
+    F = torch.as_tensor(np.asarray(F_gt, dtype=np.float64), device=dev)
+    a = torch.as_tensor(np.ascontiguousarray(first, dtype=np.float32), device=dev).unsqueeze(0)
+    b = torch.as_tensor(np.ascontiguousarray(second, dtype=np.float32), device=dev).unsqueeze(0)
+    new_a, new_b = ops.correct_matches(F, a, b)
+    return new_a.cpu().numpy(), new_b.cpu().numpy()
+
+
+def get_virt_x1x2_np(im_shape, F_gt, K, pts1_virt_b, pts2_virt_b):
+    """The virtual correspondences of the F-loss: the given points moved onto the geometry F_gt by the optimal correction
+    (utils_misc.py:173-199).  Returns numpy (pts1_virt_normalized, pts2_virt_normalized) float64 [M,3] and (pts1_virt,
+    pts2_virt) float32 [M,3], homogeneous.  Two quirks of the reference are kept:
+      - the call is correctMatches(F_gt, pts2_virt_b, pts1_virt_b) and its first output becomes pts1_virt (:176): the corrected
+        points do satisfy pts2_virt^T F_gt pts1_virt = 0, but each started from the other image's input (harmless while the
+        two grids are equal);
+      - pts2_virt_normalized is computed from pts1_virt, not pts2_virt (:198).
+    A point on an epipole comes back NaN from the correction and is set to 0 (:177-178)."""
+    pts1_virt, pts2_virt = _correct_matches_np(F_gt, pts2_virt_b, pts1_virt_b)
+    pts1_virt[np.isnan(pts1_virt)] = 0.
+    pts2_virt[np.isnan(pts2_virt)] = 0.
+    pts1_virt = homo_np(pts1_virt[0])
+    pts2_virt = homo_np(pts2_virt[0])
+    pts1_virt_normalized = (np.linalg.inv(K) @ pts1_virt.T).T
+    pts2_virt_normalized = (np.linalg.inv(K) @ pts1_virt.T).T  # sic: from pts1_virt (:198)
+    return pts1_virt_normalized, pts2_virt_normalized, pts1_virt, pts2_virt
+
+
+def get_virt_x1x2(im_shape, F_gt, K, pts1_virt_b=None, pts2_virt_b=None):
+    """get_virt_x1x2_np with the grid of im_shape as the default points and float32 CPU tensors returned, as the reference's
+    loader stores them (utils_misc.py:201-230; same two quirks, :206 and :228)."""
+    if pts1_virt_b is None and pts2_virt_b is None:
+        pts1_virt_b, pts2_virt_b = get_virt_x1x2_grid(im_shape)
+    pts1_virt_normalized, pts2_virt_normalized, pts1_virt, pts2_virt = get_virt_x1x2_np(im_shape, F_gt, K, pts1_virt_b, pts2_virt_b)
+    return torch.from_numpy(pts1_virt_normalized).float(), torch.from_numpy(pts2_virt_normalized).float(), \
+        torch.from_numpy(pts1_virt).float(), torch.from_numpy(pts2_virt).float()
+
+
+_virt_grids = {}  # (device, im_shape) -> the grid [100,2] on that device
+
+
+def get_virt_x1x2_batch(im_shape, F_gts, Ks):
+    """get_virt_x1x2 for a batch that is already on the device: F_gts, Ks [B,3,3] -> (pts1_virt_normalized,
+    pts2_virt_normalized, pts1_virt, pts2_virt), each [B,100,3] float32 on F_gts' device -- what a training step feeds
+    get_all_loss_DeepF as pts*_virt_normalized / pts*_virt_ori instead of carrying them through the loader.  One launch for the
+    batch, the grid cached per (device, im_shape), no host synchronisation.  F_gts is used in float64 if it is given so (the
+    correction reads F in fp64); inv(K) @ x is computed in float64 like the reference's numpy, then rounded.  Both quirks of
+    get_virt_x1x2_np are kept."""
+    dev = F_gts.device
+    key = (dev, tuple(int(v) for v in im_shape[:2]))
+    grid = _virt_grids.get(key)
+    if grid is None:
+        grid = _virt_grids[key] = torch.as_tensor(get_virt_x1x2_grid(im_shape)[0], device=dev)
+    B = F_gts.shape[0]
+    pts_b = grid.unsqueeze(0).expand(B, -1, -1)
+    pts1_virt, pts2_virt = ops.correct_matches(F_gts, pts_b, pts_b)  # correctMatches(F_gt, pts2_virt_b, pts1_virt_b): equal grids
+    pts1_virt = _homo(torch.where(torch.isnan(pts1_virt), torch.zeros_like(pts1_virt), pts1_virt))
+    pts2_virt = _homo(torch.where(torch.isnan(pts2_virt), torch.zeros_like(pts2_virt), pts2_virt))
+    # inv(K) by cofactors in float64: row i of the inverse is the cross product of the two other columns over the determinant
+    K = Ks.to(torch.float64)
+    c0, c1, c2 = K[:, :, 0], K[:, :, 1], K[:, :, 2]
+    r0 = torch.linalg.cross(c1, c2)
+    K_inv = torch.stack((r0, torch.linalg.cross(c2, c0), torch.linalg.cross(c0, c1)), 1) / (c0 * r0).sum(1)[:, None, None]
+    pts1_virt_normalized = (pts1_virt.double() @ K_inv.transpose(1, 2)).float()
+    pts2_virt_normalized = pts1_virt_normalized.clone()  # sic: from pts1_virt (:228)
+    return pts1_virt_normalized, pts2_virt_normalized, pts1_virt, pts2_virt

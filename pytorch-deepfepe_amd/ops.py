@@ -1057,6 +1057,33 @@ def ransac_essential_pose(matches: Tensor, K: Tensor, threshold: float = 1.0, co
     return out
 
 
+def correct_matches(F: Tensor, pts1: Tensor, pts2: Tensor, want_cost: bool = False):
+    """The optimal correction of correspondences onto an epipolar geometry (Hartley & Sturm), cv2.correctMatches(F, pts1, pts2)
+    for a batch: new1, new2 [B,M,2] float32 with new2^T F new1 = 0 and |pts1 - new1|^2 + |pts2 - new2|^2 minimal; with want_cost
+    also that minimum [B,M] in px^2.  F [B,3,3], or [3,3] for all pairs, of any float dtype: it is converted to float64, which the
+    kernel reads (include/dfepe.h says why).  pts1, pts2 [B,M,2] pixels on the GPU.  A point on an epipole gives NaN, as in cv2.
+    One launch, no host synchronisation, no autograd: these are ground-truth data."""
+    p, q = _prep(pts1.detach(), "pts1"), _prep(pts2.detach(), "pts2")
+    _shape(p, "pts1 (pixel x, y)", None, None, 2)
+    B, M = p.shape[0], p.shape[1]
+    _shape(q, "pts2", B, M, 2)
+    if not F.is_cuda:
+        raise _lib.DfepeError("F must live on the GPU (this package has no CPU path)")
+    Fd = F.detach().to(torch.float64).contiguous()
+    if Fd.dim() == 2:
+        _shape(Fd, "F", 3, 3)
+    else:
+        _shape(Fd, "F", B, 3, 3)
+    dev = p.device
+    new1, new2 = torch.empty(B, M, 2, device=dev), torch.empty(B, M, 2, device=dev)
+    cost = torch.empty(B, M, device=dev) if want_cost else None
+    with _on(dev):
+        rc = _lib.lib().dfepe_correct_matches(_stream(), _ptr(Fd), 0 if Fd.dim() == 2 else 9, _ptr(p), _ptr(q), B, M, _ptr(new1),
+                                              _ptr(new2), _ptr(cost))
+    _lib.check(rc, "dfepe_correct_matches")
+    return (new1, new2, cost) if want_cost else (new1, new2)
+
+
 # ------------------------------------------------------------------------------------------------
 # validation summary reductions ("next" row f-2)
 # ------------------------------------------------------------------------------------------------

@@ -10,7 +10,8 @@ It follows the *input contract* of the reference's training batch
   qs_cam [B,4,1], ts_cam [B,3,1]   quaternion / translation of the *camera* motion (inverse of the above)
   pts1_virt_ori, pts2_virt_ori [B,M,3]  homogeneous pixel "virtual" correspondences lying exactly on the
                                         ground-truth epipolar geometry (stand-in for cv2.correctMatches grid,
-                                        deepFEPE/dsac_tools/utils_misc.py:163-199)
+                                        deepFEPE/dsac_tools/utils_misc.py:163-199; the real generator is
+                                        compat.utils_misc.get_virt_x1x2_batch over ops.correct_matches)
 There is no dataset and no OpenCV in this environment, so everything is generated.
 """
 from __future__ import annotations
