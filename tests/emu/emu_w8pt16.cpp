@@ -82,7 +82,10 @@ struct FwdBody {
 };
 template <int IT, bool RAW>
 struct BwdBody {
-  static void run(const W8BwdArgs& A, int pair, double* xch) { w8pt16_bwd_pair<IT, RAW>(A, pair, xch); }
+  static void run(const W8BwdArgs& A, int pair, double* xch) {
+    // un-normalised rows: the non-plain build, weight gradients only (w8pt16.hip: dfepe_w8pt16_bwd_launch)
+    if (A.variant != 0) w8pt16_bwd_pair_impl<IT, RAW, false, false>(A, pair, xch); else w8pt16_bwd_pair<IT, RAW>(A, pair, xch);
+  }
 };
 }  // namespace
 
@@ -101,7 +104,7 @@ extern "C" int emu_w8pt16_bwd(const float* pts1, const float* pts2, const float*
                               unsigned flags, float image_w, float image_h, float clamp_at, const float* save,
                               const float* F_out, const float* g_F, const float* g_residual, const float* g_epi,
                               const float* g_weights_extra, const float* g_scale, float* g_weights, float* g_pts1, float* g_pts2) {
-  if (N < 1) return -3;
+  if (N < 1 || ((flags & DFEPE_W8PT_NO_ROWNORM) && g_pts1 != nullptr)) return -3;
   const W8BwdArgs A = w8_bwd_args_of(pts1, pts2, weights, B, N, n_weight_sets, flags, image_w, image_h, clamp_at, save, F_out, g_F, g_residual,
                                      g_epi, g_weights_extra, g_scale, g_weights, g_pts1, g_pts2, nullptr);
   return dispatch<BwdBody>(A, (flags & DFEPE_W8PT_RAW_MATCHES) != 0);

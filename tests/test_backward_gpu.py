@@ -201,11 +201,14 @@ def test_fused_step_equals_unfused_ops(dfepe):
     np.testing.assert_allclose(a["packed"].cpu().numpy(), ref.cpu().numpy(), rtol=1e-6)
 
 
-@pytest.mark.parametrize("B,N,batched", [(37, 100, False), (300, 100, True), (5, 200, False)])
+@pytest.mark.parametrize("B,N,batched", [(37, 100, False), (300, 100, True), (5, 200, False),
+                                         (19, 16, False), (19, 32, True), (19, 64, False), (19, 128, True), (3073, 129, False)])
 def test_deferred_loss_head_gives_the_same_step(dfepe, B, N, batched):
     """defer_loss_head: the batch sums of the loss tail are finished by the first backward launch (three spare wavefronts of
     its first workgroup for the row kernels; a launch behind it for the cooperative kernels, N = 200 at B = 5) instead
-    of a launch of their own.  After backward every output and the gradients are those of the undeferred step, bit for bit."""
+    of a launch of their own.  After backward every output and the gradients are those of the undeferred step, bit for bit.
+    The head-riding build exists for every rung: N = 16, 32, 64, 128 (IT 1, 2, 4, 8; 100 is IT 7) and N = 129 past the cooperative
+    pair limit (3073 pairs: the row kernel that re-reads its correspondences, IT 0)."""
     depth = 5
     sc = dfepe.pipeline.scene_to_device(dfepe.synth.make_scene(B, N, seed=41, outlier_ratio=0.3, depth_layers=depth), DEV)
 
@@ -291,10 +294,11 @@ def test_fused_loss_tail_equals_the_five_kernel_tail(dfepe, qt, balance_F):
     assert torch.equal(a2["packed"], a["packed"]) and torch.equal(a2["grad_logits"], a["grad_logits"])
 
 
-def test_layers_batched_launch_is_bit_identical(dfepe):
+@pytest.mark.parametrize("N", [100, 16, 64, 128])
+def test_layers_batched_launch_is_bit_identical(dfepe, N):
     """n_weight_sets = L (all layers' weightings of the same pairs in one grid) runs the same per-wave program as L
     separate launches: every output and the logits gradient are bit-identical.  Point gradients are refused there."""
-    B, N, depth = 37, 100, 5
+    B, depth = 37, 5
     sc = dfepe.pipeline.scene_to_device(dfepe.synth.make_scene(B, N, seed=7, outlier_ratio=0.4, depth_layers=depth), DEV)
     a = dfepe.pipeline.hot_path_step(sc, IMAGE_SIZE, depth, 0.02, qt=True, fused=True)
     b = dfepe.pipeline.hot_path_step(sc, IMAGE_SIZE, depth, 0.02, qt=True, fused=True, layers_batched=True)

@@ -5,10 +5,15 @@ the GPU box by tests/test_rowgroup_gpu.py.  The emulation library is test infras
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fit_adjoint_cases as fac  # noqa: E402
+import pose_branch_cases as pbc  # noqa: E402
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EMU_DIR = os.path.join(REPO, "tests", "emu")
@@ -22,7 +27,8 @@ def emu():
     os.makedirs(out, exist_ok=True)
     lib = os.path.join(out, "libemu_w8pt16.so")
     srcs = [os.path.join(EMU_DIR, "emu_w8pt16.cpp"), os.path.join(EMU_DIR, "rowgroup.h")] + [
-        os.path.join(REPO, "pytorch-deepfepe_amd", "csrc", f) for f in ("w8pt16_body.h", "w8pt16_bwd_body.h", "loss_tail_body.h", "dfepe_math.h", "fit_plan.h")]
+        os.path.join(REPO, "pytorch-deepfepe_amd", "csrc", f) for f in ("w8pt16_body.h", "w8pt16_bwd_body.h", "loss_tail_body.h", "pose_math.h", "dfepe_math.h", "fit_plan.h")] + [
+        os.path.join(REPO, "include", "dfepe.h")]
     if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in srcs):
         subprocess.run(["g++", "-O1", "-std=c++17", "-shared", "-fPIC", f"-I{EMU_DIR}", f"-I{REPO}/pytorch-deepfepe_amd/csrc",
                         f"-I{REPO}/include", srcs[0], "-o", lib], check=True)
@@ -56,13 +62,13 @@ def emu_fwd(L, pts1, pts2, w, flags, want_epi=True, want_save=True, clamp_at=0.5
     return F, res, epi, save, wout
 
 
-def emu_bwd(L, pts1, pts2, w, flags, save, F, gF, gRes, gEpi, want_pts=False, clamp_at=0.5, g_scale=None):
+def emu_bwd(L, pts1, pts2, w, flags, save, F, gF, gRes, gEpi, want_pts=False, clamp_at=0.5, g_scale=None, gW_extra=None):
     B, N = w.shape
     gW = torch.empty(B, N)
     gP1 = torch.empty_like(pts1) if want_pts else None
     gP2 = torch.empty_like(pts2) if (want_pts and pts2 is not None) else None
     rc = L.emu_w8pt16_bwd(_p(pts1), _p(pts2), _p(w), B, N, 1, flags, float(IMAGE_SIZE[1]), float(IMAGE_SIZE[0]), clamp_at,
-                          _p(save), _p(F), _p(gF), _p(gRes), _p(gEpi), None, _p(g_scale), _p(gW), _p(gP1), _p(gP2))
+                          _p(save), _p(F), _p(gF), _p(gRes), _p(gEpi), _p(gW_extra), _p(g_scale), _p(gW), _p(gP1), _p(gP2))
     assert rc == 0
     return gW, gP1, gP2
 
@@ -240,7 +246,8 @@ def relerr(a, b):
     return np.abs(a - b).max() / (np.abs(b).max() + 1e-300)
 
 
-@pytest.mark.parametrize("N,outl", [(100, 0.0), (100, 0.4), (128, 0.2), (20, 0.2), (9, 0.0), (300, 0.2), (1000, 0.2), (40, 0.2), (75, 0.2), (96, 0.2)])
+@pytest.mark.parametrize("N,outl", [(100, 0.0), (100, 0.4), (128, 0.2), (20, 0.2), (9, 0.0), (300, 0.2), (1000, 0.2), (40, 0.2), (75, 0.2), (96, 0.2),
+                                    (8, 0.2), (16, 0.2), (17, 0.2), (32, 0.2), (33, 0.2), (64, 0.2), (65, 0.2), (112, 0.2), (113, 0.2), (129, 0.2)])
 @pytest.mark.parametrize("use_res,use_epi", [(False, False), (True, False), (True, True)])
 def test_backward_body_vs_oracle_autograd(emu, dfepe, oracle, N, outl, use_res, use_epi):
     """d/d(logits) of <F, GF> + <residual, GR> + <epi, GE> through the emulated w8pt16 forward + backward bodies against
@@ -271,7 +278,7 @@ def test_backward_body_vs_oracle_autograd(emu, dfepe, oracle, N, outl, use_res, 
     assert relerr(gL.numpy(), lo_in.grad.numpy()) < (2e-4 if N >= 20 else 2e-3)
 
 
-@pytest.mark.parametrize("N", [60, 200])
+@pytest.mark.parametrize("N", [60, 200, 16, 17, 112, 128])
 @pytest.mark.parametrize("raw", [True, False])
 def test_point_gradients_body_vs_oracle_autograd(emu, dfepe, oracle, raw, N):
     B = 4
@@ -306,6 +313,56 @@ def test_point_gradients_body_vs_oracle_autograd(emu, dfepe, oracle, raw, N):
     else:
         assert relerr(gP1[:, :, :2].numpy(), p1.grad[:, :, :2].numpy()) < 5e-4
         assert relerr(gP2[:, :, :2].numpy(), p2.grad[:, :, :2].numpy()) < 5e-4
+
+
+LADDER_B = 19  # two workgroups of the row kernels, the last with three pairs in one wavefront
+
+
+def ladder_seed(N):
+    return 100 + N
+
+
+@pytest.mark.parametrize("variant", list(fac.VARIANTS))
+@pytest.mark.parametrize("N", [8, 16, 17, 32, 33, 64, 65, 112, 113, 128, 129, 257])
+def test_fit_adjoint_ladder_body_vs_oracle_autograd(emu, N, variant):
+    """The cases of tests/test_backward_ladder_gpu.py (same builder, same seeds, same bounds: tests/fit_adjoint_cases.py) through the
+    emulated bodies: every rung of the N ladder and both sides of every edge, every variant of the backward.  A case that misses on
+    the GPU and passes here is a build / launch defect; one that misses in both places is in the body's source."""
+    case = fac.make_case(LADDER_B, N, ladder_seed(N), variant)
+    a = case.launch
+    flags = (RAW if a["raw"] else 0) | (LOGITS if a["logits"] else 0) | a["flags"]
+    F, res, epi, save, wout = emu_fwd(emu, a["pts1"], a["pts2"], a["weights"], flags)
+    gW, gP1, gP2 = emu_bwd(emu, a["pts1"], a["pts2"], wout if a["logits"] else a["weights"], flags, save, F, a["gF"], a["gRes"], a["gEpi"],
+                           want_pts=a["want_pts"], gW_extra=a["gW_extra"])
+    fac.check(case, F, {"weights": gW, "pts1": gP1, "pts2": gP2}, tag="emu")
+
+
+def test_loss_tail_body_on_every_quaternion_branch(emu):
+    """The 42 large-rotation cases of tests/pose_branch_cases.py (branches 0..3 of the trace-method quaternion, half of them with the
+    sign flip) through the emulated loss tail with T = K = I (E = F), coefF = 0 and clamps of 10 (no gradient gated): the four pose
+    errors against oracle.rt_loss in float64, d loss / d F against central differences of the float64 oracle."""
+    I, P, F32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
+    emu.emu_loss_tail.restype = I
+    emu.emu_loss_tail.argtypes = [P, I, I, P, P, I, P, P, P, I, F32, P, P, P, F32, F32, F32, F32, F32] + [P] * 9
+    c = pbc.make_cases()
+    L, B, M = c.L, c.B, 8
+    g = torch.Generator().manual_seed(9)
+    v1 = torch.cat((torch.randn(B, M, 2, generator=g), torch.ones(B, M, 1)), 2).contiguous()
+    v2 = torch.cat((torch.randn(B, M, 2, generator=g), torch.ones(B, M, 1)), 2).contiguous()
+    eye = torch.eye(3).contiguous()
+    Ks = torch.eye(3).repeat(B, 1, 1).contiguous()
+    coefq, coeft = 0.7, 1.3
+    loss_sum, E = torch.zeros(L, B), torch.zeros(L, B, 3, 3)
+    q_l2, t_l2, R_deg, t_deg = (torch.zeros(L, B) for _ in range(4))
+    sel = torch.zeros(L, B, dtype=torch.int32)
+    gF = torch.zeros(L, B, 3, 3)
+    part = torch.zeros(B, 48, dtype=torch.float64)
+    rc = emu.emu_loss_tail(_p(c.E), L, B, _p(eye), _p(eye), 0, _p(Ks), _p(v1), _p(v2), M, 0.02, _p(c.q_gt), _p(c.t_gt), _p(c.R_gt),
+                           10.0, 10.0, 0.0, coefq, coeft, _p(loss_sum), _p(E), _p(q_l2), _p(t_l2), _p(R_deg), _p(t_deg), _p(sel), _p(gF), _p(part))
+    assert rc == 0
+    assert torch.equal(E, c.E)  # T = K = I: the matrix that is decomposed is the one given
+    pbc.check_forward(c, q_l2, t_l2, R_deg, t_deg, tag="emu")
+    pbc.check_adjoint(c, gF, coefq, coeft, tag="emu")
 
 
 @pytest.mark.parametrize("L,M,qt,noise", [(5, 100, True, 0.003), (3, 100, False, 0.003), (2, 17, True, 0.02), (4, 128, True, 0.0005)])
