@@ -325,6 +325,8 @@ int dfepe_metrics_summary(const float *epi_est, const float *epi_gt, size_t n_ep
  *         0 in its 2-D branch), 1 = _sampson_dist, 2 = _epi_distance (writes 3 planes: mean, d1, d2);
  *         | DFEPE_EPI_HOMOGENEOUS: X, Y are [B,N,3] homogeneous points used as they are (if_homo=True), else [B,N,2]
  *   F [B,9]; out [B,N] (kind 0,1) or [3,B,N] (kind 2); clamp_at < 0 means no clamp (clamp_at=None; kind 0 only)
+ *   a point with F x = 0 (or F^T y = 0) gives what the float64 formula gives, NaN (0 * inf, 0 / 0) included; the clamp keeps a NaN,
+ *   as torch.clamp does
  */
 #define DFEPE_EPI_HOMOGENEOUS 8
 int dfepe_epi_metrics(int kind, const float *F, const float *X, const float *Y, int B, int N, float clamp_at,

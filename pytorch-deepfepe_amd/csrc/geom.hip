@@ -99,7 +99,9 @@ epi_metrics_kernel(int kind, const float* __restrict__ F, const float* __restric
   const double a = fx[0] * fx[0] + fx[1] * fx[1], bq = fty[0] * fty[0] + fty[1] * fty[1];
   if (kind == 0) {
     double e = num * num * (1.0 / (a + (double)eps) + 1.0 / (bq + (double)eps));
-    if (clamp_at >= 0.f) e = fmin(e, (double)clamp_at);  // negative: no clamp (clamp_at=None)
+    // negative: no clamp (clamp_at=None).  A NaN (0 * inf where F x = 0 and eps = 0) stays a NaN like under torch.clamp
+    // (utils_F.py:336-337); fmin would return the bound instead.
+    if (clamp_at >= 0.f && e > (double)clamp_at) e = (double)clamp_at;
     out[idx] = (float)e;
   } else if (kind == 1) {
     out[idx] = (float)(num * num / (a + bq));
