@@ -602,6 +602,38 @@ int dfepe_gather_matches(const float *pts1, const float *pts2, const float *off1
                          float *xs, float *offsets, float *quality, void *stream);
 
 /*
+ * Ratio-test 2-NN descriptor matching: the correspondence source of the SIFT-based configs.
+ * Replaces the per-pair host call KNN_match (deepFEPE/dsac_tools/utils_opencv.py:39-90, if_BF=True):
+ *   cv2.BFMatcher(NORM_L2).knnMatch(des1, des2, k=2)  (:44-45)  and Lowe's ratio test
+ *   `m.distance < 0.8 * n.distance`  (:63-67)  -> dfepe_knn_match, batched over the pairs.  The FLANN branch (if_BF=False:
+ *   randomised kd-trees, 50 checks) is approximate and not reproducible; this exact search stands in for it too.
+ *
+ *   desc1 [B,N1,D], desc2 [B,N2,D]  descriptors of any norm, fp32, row-major, 16-byte aligned; D a multiple of 32 (else
+ *                                   UNSUPPORTED; SIFT: 128).  NaN components are out of scope.
+ *   ratio, ratio_test               ratio_test != 0: row i is good when (double)dist1[i] < ratio * (double)dist2[i], the
+ *                                   product in double as Python evaluates the reference's line (NaN ratio: INVALID_ARG);
+ *                                   ratio_test == 0: every row is good (if_ratio_test=False) and ratio is ignored
+ *   workspace                       dfepe_knn_match_workspace_bytes(B,N1,N2) bytes, 8-byte aligned, contents irrelevant
+ *   nn1, nn2 [B,N1] int32           the two columns of desc2 nearest to row i, ordered by (distance, column index): ties keep
+ *                                   the lower index first, like OpenCV's k-best insertion (strict < over increasing columns)
+ *   dist1, dist2 [B,N1] fp32        their L2 distances: sqrtf of the fp32 squared distance max(|a|^2 + |b|^2 - 2 a.b, 0)
+ *   m_idx1, m_idx2 [B,N1] int32, score [B,N1] fp32: the first count[b] entries of row b are the good rows (i, nn1[i], dist1[i])
+ *                                   of pair b in increasing i (the reference's good_ij); the rest is not written.  The layout
+ *                                   of dfepe_nn_match_two_way: dfepe_gather_matches takes it unchanged.   count [B] int32.
+ * all_ij of the reference is (i, nn1[i]) for every i.  N2 < 2 with N1 > 0 has no second neighbour: INVALID_ARG (the reference's
+ * `for m, n in matches` raises ValueError).  N1 == 0: count is zeroed, nothing else is written.  B == 0: OK, nothing happens.
+ * More than 2^31 - 1 tiles of 128 x 128 over the batch: UNSUPPORTED.  All refusals are made before anything is launched.
+ * The distance matrix is never materialised: fp32 MFMA tiles (exact fp32 products), the squared norms accumulated by one fmaf
+ * per component in increasing order, t = fma(-2, a.b, |a|^2 + |b|^2); |t - exact| <= (2 D + 3) 2^-23 (max|a|^2 + max|b|^2).
+ * Every 64-column strip writes its two best keys per row to its own workspace slot (no atomics, no memset): results do not
+ * depend on the launch order and two calls on the same input are bit-identical.
+ */
+size_t dfepe_knn_match_workspace_bytes(int B, int N1, int N2);
+int dfepe_knn_match(const float *desc1, const float *desc2, int B, int N1, int N2, int D, double ratio, int ratio_test,
+                    void *workspace, int *nn1, int *nn2, float *dist1, float *dist2, int *m_idx1, int *m_idx2, float *score,
+                    int *count, void *stream);
+
+/*
  * Robust fundamental matrix of every pair: OpenCV 3.4 findFundamentalMat(x1, x2, FM_RANSAC, threshold, confidence, max_iters),
  * batched.  Replaces: cv2.findFundamentalMat(x1, x2, cv2.RANSAC, 0.1) in utils_opencv.recover_camera_opencv
  * (deepFEPE/dsac_tools/utils_opencv.py:157), the validation baseline of val_rt (train_good_utils.py:615-633).

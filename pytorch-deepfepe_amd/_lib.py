@@ -100,6 +100,8 @@ _SIGNATURES = {
     "dfepe_nn_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_nn_match_two_way": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P]),
     "dfepe_gather_matches": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    "dfepe_knn_match_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_knn_match": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_double, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_ransac_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_ransac_fundamental": (c_int, [_P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_ransac_in_front": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),

@@ -4,7 +4,13 @@ utils_opencv.py:129-208), backed by the batched RANSAC estimator of libdfepe_hip
 What differs from OpenCV: the random stream (include/dfepe.h, dfepe_ransac_fundamental), so results agree with cv2's in
 distribution, not bit for bit.  The five-point baseline (cv2.findEssentialMat, Nister's solver) is recover_camera_five_point,
 backed by ops.ransac_essential_pose; recover_camera_opencv(five_point=True) itself still raises.  Not built: LMedS (OpenCV's
-choice for fewer than 15 correspondences of the 8-point branch)."""
+choice for fewer than 15 correspondences of the 8-point branch).
+
+KNN_match (utils_opencv.py:39-90) is backed by ops.knn_match: the exact k = 2 search of cv2.BFMatcher(NORM_L2).knnMatch with
+Lowe's ratio test.  What differs from OpenCV: ``if_BF=False`` selects FLANN's randomised kd-trees (5 trees, 50 checks) in the
+reference, an approximate search whose answer is not reproducible; here both values of ``if_BF`` run the exact search, so the
+FLANN branch's occasional misses do not occur.  Near-ties inside the float32 error of the distance (include/dfepe.h,
+dfepe_knn_match) may be ordered differently from OpenCV's own float32 summation."""
 import numpy as np
 import torch
 
@@ -99,3 +105,51 @@ def recover_camera_five_point(K, x1, x2, delta_Rtij_inv, threshold=0.1, show_res
         print("Recovered by OpenCV %s (camera): The rotation error (degree) %.4f, and translation error (degree) %.4f"
               % ("5 point" + method_app, err[0], err[1]))
     return M, err, mask2, out["E"][0].cpu().double().numpy()
+
+
+def KNN_match(des1, des2, x1_all, x2_all, kp1, kp2, img1_rgb, img2_rgb, visualize=False, if_BF=False, if_ratio_test=True):
+    """Same call and return as the reference (utils_opencv.py:39-90), numpy in and out: (x1 [n,2], x2 [n,2], all_ij [N1,2],
+    good_ij [n,2]) from one launch.  des1 [N1,D], des2 [N2,D] (D a multiple of 32; SIFT: 128); the ratio is the reference's 0.8,
+    evaluated as its Python line does (float64).  ``if_BF`` is accepted and ignored: the search is always the exact one (module
+    docstring).  ``kp1``, ``kp2``, ``img1_rgb``, ``img2_rgb`` are accepted and unused; ``visualize=True`` needs cv2 and
+    matplotlib and raises NotImplementedError.  N2 < 2 raises ValueError like the reference's ``for m, n in matches``."""
+    if visualize:
+        raise NotImplementedError("KNN_match(visualize=True): drawing the matches needs cv2 and matplotlib, which are not used here")
+    des1, des2 = np.asarray(des1, dtype=np.float32), np.asarray(des2, dtype=np.float32)
+    x1_all, x2_all = np.asarray(x1_all), np.asarray(x2_all)
+    N1 = des1.shape[0]
+    if N1 == 0:
+        empty = np.zeros((0, 2), dtype=np.int64)
+        return x1_all[:0], x2_all[:0], empty, empty.copy()
+    dev = torch.device("cuda")
+    out = ops.knn_match(torch.tensor(des1, device=dev).unsqueeze(0), torch.tensor(des2, device=dev).unsqueeze(0), ratio=0.8,
+                        ratio_test=bool(if_ratio_test))
+    nn1, m1, m2 = (out[k][0].cpu().numpy().astype(np.int64) for k in (0, 4, 5))
+    cnt = int(out[7][0].item())
+    good_ij = np.stack((m1[:cnt], m2[:cnt]), axis=1)
+    all_ij = np.stack((np.arange(N1, dtype=np.int64), nn1), axis=1)
+    x1, x2 = x1_all[good_ij[:, 0], :], x2_all[good_ij[:, 1], :]
+    print("# good points: %d/(%d, %d)" % (cnt, des1.shape[0], des2.shape[0]))
+    return x1, x2, all_ij, good_ij
+
+
+def KNN_match_batch(des1, des2, x1_all, x2_all, ratio=0.8, out_num_points=None):
+    """KNN_match for a whole batch on the device: des1 [B,N1,D], des2 [B,N2,D], x1_all [B,N1,2], x2_all [B,N2,2] tensors.
+    Returns the dict of ops.knn_match's outputs (nn1, nn2, dist1, dist2, m_idx1, m_idx2, score, count).  With ``out_num_points``
+    it also holds xs [B,n,4] and quality [B,n,2] = (distance, dist1 / dist2) of the good matches cropped or padded to n per pair:
+    the permutation is drawn on the host by utils_misc.crop_or_pad_choice (numpy's RNG, as matches_from_SP_outputs does) and
+    gathered by ops.gather_matches.  A pair without a good match cannot be padded: crop_or_pad_choice's error propagates."""
+    from .utils_misc import crop_or_pad_choice
+
+    nn1, nn2, dist1, dist2, m1, m2, sc, cnt = ops.knn_match(des1, des2, ratio=ratio, ratio_test=True)
+    out = {"nn1": nn1, "nn2": nn2, "dist1": dist1, "dist2": dist2, "m_idx1": m1, "m_idx2": m2, "score": sc, "count": cnt}
+    if out_num_points is None:
+        return out
+    counts = cnt.cpu().numpy()
+    choice = np.stack([crop_or_pad_choice(int(n), out_num_points, shuffle=True) for n in counts]).astype(np.int32)
+    choice_dev = torch.from_numpy(choice).to(m1.device)
+    xs, _, q = ops.gather_matches(x1_all, x2_all, None, None, m1, m2, sc, choice_dev)
+    rows = torch.gather(m1, 1, choice_dev.long()).long()  # every position of choice is below the pair's count
+    out["xs"] = xs
+    out["quality"] = torch.cat((q, torch.gather(dist1 / dist2, 1, rows).unsqueeze(-1)), dim=2)
+    return out

@@ -1200,6 +1200,33 @@ def nn_match_two_way(desc1: Tensor, desc2: Tensor, nn_thresh: float):
     return m1, m2, sc, cnt
 
 
+def knn_match(desc1: Tensor, desc2: Tensor, ratio: float = 0.8, ratio_test: bool = True):
+    """desc1 [B,N1,D], desc2 [B,N2,D] descriptors of any norm -> (nn1, nn2 [B,N1] int32, dist1, dist2 [B,N1], m_idx1, m_idx2
+    [B,N1] int32, score [B,N1], count [B] int32): per row the two nearest columns of desc2 by (L2 distance, column index) and
+    their distances; the first count[b] entries of m_idx1 / m_idx2 / score are the rows that pass Lowe's ratio test
+    ``float64(dist1) < ratio * float64(dist2)`` (all rows with ``ratio_test=False``) in increasing row order, in the layout
+    ``gather_matches`` takes (KNN_match with if_BF=True, dsac_tools/utils_opencv.py:39-90, for all pairs)."""
+    d1, d2 = _prep(desc1, "desc1"), _prep(desc2, "desc2")
+    if d1.dim() != 3 or d2.dim() != 3 or d1.shape[0] != d2.shape[0] or d1.shape[2] != d2.shape[2]:
+        raise ValueError("descriptors must be [B,N1,D] and [B,N2,D]")
+    B, N1, D = d1.shape
+    N2 = d2.shape[1]
+    if N2 < 2:
+        raise ValueError("knn_match needs at least two descriptors in desc2 (k = 2)")
+    L = _lib.lib()
+    dev = d1.device
+    n = max(N1, 1)
+    nn1, nn2, m1, m2 = (torch.empty(B, n, device=dev, dtype=torch.int32) for _ in range(4))
+    dist1, dist2, sc = (torch.empty(B, n, device=dev, dtype=torch.float32) for _ in range(3))
+    cnt = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty(max(int(L.dfepe_knn_match_workspace_bytes(B, N1, N2)) // 8, 1), device=dev, dtype=torch.int64)
+    with _on(dev):
+        rc = L.dfepe_knn_match(_ptr(d1), _ptr(d2), B, N1, N2, D, float(ratio), int(bool(ratio_test)), _ptr(ws), _ptr(nn1), _ptr(nn2),
+                               _ptr(dist1), _ptr(dist2), _ptr(m1), _ptr(m2), _ptr(sc), _ptr(cnt), _stream())
+    _lib.check(rc, "dfepe_knn_match")
+    return nn1, nn2, dist1, dist2, m1, m2, sc, cnt
+
+
 def gather_matches(pts1: Tensor, pts2: Tensor, off1: Optional[Tensor], off2: Optional[Tensor], m_idx1: Tensor, m_idx2: Tensor,
                    score: Tensor, choice: Tensor):
     """choice [B,n_out] int32 positions into each pair's match list -> xs [B,n_out,4], offsets [B,n_out,4] | None,
