@@ -753,6 +753,60 @@ int dfepe_ransac_essential(const float *matches, const float *K, int B, int N, d
 int dfepe_correct_matches(void *stream, const double *F, long f_stride, const float *p, const float *q, int B, int M, float *p_out,
                           float *q_out, float *cost);
 
+/*
+ * Odometry evaluation, part 1: relative poses -> trajectory.  Replaces Exp_table_processor.get_abs_poses
+ * (deepFEPE/utils/eval_tools.py:268-284: last = pose @ last; abs.append(inv(last)[:3]); the identity first) and, with cam2body,
+ * the camera-to-body conjugation in front of it (relative_pose_cam_to_body, Train_model_pipeline.py:1098-1108:
+ * inv(Rt_cam2_gt) @ M @ Rt_cam2_gt, collected as relative_poses_body at :1110-1119).  Everything is fp64; a pose is a 3x4 affine
+ * map, row-major, with the implied last row (0, 0, 0, 1).
+ *   stream comes first (a hipStream_t).
+ *   rel [S,n_max,12]: the relative poses P_1 .. P_n of each sequence; lengths [S] int32 or NULL (every sequence has n_max poses);
+ *     a length is clamped to [0, n_max].
+ *   cam2body: NULL, or [S,n_max,12] with c2b_stride = 12 (one per pose), or [S,12] with c2b_stride = 0 (one per sequence); any
+ *     other stride is INVALID_ARG.  With it P_k is replaced by inv(C) P_k C (general inverse, evaluated left to right).
+ *   abs_out [S,n_max+1,12]: entry 0 is the identity, entry k is inv(P_k ... P_1) -- the general inverse (adjugate over
+ *     determinant, then -A^-1 t), not the transpose, as numpy.linalg.inv in the reference.  Entries past lengths[s] are not
+ *     written.
+ *   S < 0, n_max < 0: INVALID_ARG; S == 0 returns 0 before any launch; then a NULL abs_out, or a NULL rel with n_max > 0, is
+ *   INVALID_ARG; n_max >= 2^31 / 12 - 1: UNSUPPORTED.
+ * One workgroup of 256 lanes per sequence, tiles of 256 x 8 poses: every lane composes its 8 consecutive poses in order, the lane
+ * totals are scanned with wavefront shuffles and the wavefront totals through LDS (the later operand always on the left), and every
+ * lane walks its poses again from its prefix, inverts and stores.  No atomics, no dependence on arrival order: the result is the
+ * same bits on every run, and its first 8 entries are those of the sequential loop.  Floating-point contraction is off in this
+ * code (csrc/odometry_math.h says why).
+ */
+int dfepe_pose_chain(void *stream, const double *rel, const int *lengths, const double *cam2body, long c2b_stride, int S, int n_max,
+                     double *abs_out);
+
+/*
+ * Odometry evaluation, part 2: the snippet ATE / RE.  Replaces Exp_table_processor.pose_seq_ate (eval_tools.py:334-375) with its
+ * compensate_poses (:252-265) and compute_pose_error (:309-331), as notebooks/exp_process_table.ipynb calls it
+ * (pose_seq_ate(poses_abs_tmp, poses_gt, 5)).  fp64 throughout; the errors are rounded to fp32 because the reference's array is.
+ *   est, gt [S,m_max,12] absolute poses; windows [S] int32: the number of windows of each sequence, window w covering poses
+ *     w .. w + L - 1.  The reference scores len(est) - L windows -- it never scores the last one -- so that is what its mirror
+ *     passes; 1 scores a single snippet.  windows[s] + L - 1 <= the number of valid poses of sequence s is the CALLER's
+ *     contract: it cannot be checked without a synchronisation (the value is clamped to [0, min(W, m_max - L + 1)], so nothing is
+ *     read or written outside the buffers, but poses past a sequence's own length are the caller's padding).
+ *   W: the window capacity of the outputs; L = seq_length, 1 <= L <= 64 (anything else: UNSUPPORTED).
+ *   no_compensate != 0: the poses are scored as given (a stand-alone compute_pose_error); 0: each window of est and of gt first
+ *     goes through compensate_poses: the window's first translation is subtracted from every translation, then every pose, all
+ *     four columns, is multiplied from the left by the general inverse of the window's first 3x3.
+ *   compute_pose_error is called as (est_snip, gt_snip) on parameters named (gt, pred), so:
+ *     scale = sum(est_t . gt_t) / sum(gt_t^2);  ATE = |est_t - scale gt_t| / L;
+ *     RE = (sum_i atan2(|(R01 - R10, R12 - R21, R02 - R20)|, tr R - 1)) / L,  R = est_R inv(gt_R).
+ *     Ground-truth translations that are all zero give NaN / inf as numpy does.
+ *   errors [S,W,2] fp32 (ATE, RE); scale [S,W] fp64; aligned [S,W,12] fp64: est[w] as given with its translation times scale;
+ *   compensated [S,W,L,12] fp64 or NULL: the compensated estimate of every window (with no_compensate: the window as given);
+ *   rows w >= windows[s] are not written.  stats [S,4] fp64: (ATE mean, ATE std, RE mean, RE std), the mean and the population
+ *   standard deviation of the fp32-rounded errors of the sequence's windows, two passes in a fixed order (each lane its own
+ *   windows ascending, then a binary tree over the lanes), no atomics; NaN for a sequence without windows.
+ *   S, m_max, W < 0: INVALID_ARG; S == 0 returns 0 before any launch; then NULL windows or stats, and with W > 0 NULL est, gt,
+ *   errors, scale or aligned, are INVALID_ARG.  (S > 0 with W == 0 still launches: it writes the NaN statistics.)
+ * One workgroup per sequence, one lane per window.
+ */
+int dfepe_snippet_errors(void *stream, const double *est, const double *gt, const int *windows, int S, int m_max, int W, int L,
+                         int no_compensate, float *errors, double *scale, double *aligned, double *compensated, double *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,9 @@ TAIL_MAX_LAYERS = 16  # dfepe_loss_tail: layers per launch (kTailMaxLayers, csrc
 EPI_HOMOGENEOUS = 8
 CHEIR_FP64_ONLY = 1
 RANSAC_MIN_N = 15  # dfepe_ransac_fundamental: below, OpenCV switches to LMedS (not built)
+POSE_CHAIN_THREADS = 256  # dfepe_pose_chain: lanes per sequence (kChainThreads, csrc/odometry.hip)
+POSE_CHAIN_CHUNK = 8  # ... and consecutive poses per lane and tile (kChainChunk): a tile is 2048 poses
+SNIPPET_MAX_L = 64  # dfepe_snippet_errors: longest snippet (kSnipMaxL)
 RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked models of the one sample (not built)
 
 _P = c_void_p
@@ -108,6 +111,8 @@ _SIGNATURES = {
     "dfepe_ransac5_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_ransac_essential": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_correct_matches": (c_int, [_P, _P, c_long, _P, _P, c_int, c_int, _P, _P, _P]),
+    "dfepe_pose_chain": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P]),
+    "dfepe_snippet_errors": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -12,10 +12,13 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.dsac_tools.utils_opencv    ->   compat.utils_opencv    (recover_camera_opencv: the 8-point RANSAC baseline, no cv2)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)
+    deepFEPE.utils.eval_tools           ->   compat.eval_tools      (Exp_table_processor's odometry methods: get_abs_poses,
+                                                                    compensate_poses, compute_pose_error, pose_seq_ate; plus
+                                                                    relative_pose_cam_to_body and the on-device odometry_summary)
 
     (no counterpart: the reference's agent is eager)  compat.CapturedStep  (its training step as one replayed hipGraph)
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, dsac, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv  # noqa: F401
+from . import DeepFNet, ErrorEstimators, captured, dsac, eval_tools, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv  # noqa: F401
 from .captured import CapturedStep  # noqa: F401

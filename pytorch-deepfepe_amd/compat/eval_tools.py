@@ -1,0 +1,159 @@
+"""Mirror of the odometry evaluation of deepFEPE/utils/eval_tools.py (Exp_table_processor: compensate_poses :252-265,
+get_abs_poses :268-284, compute_pose_error :309-331, pose_seq_ate :334-375) and of the camera-to-body step in front of it
+(relative_pose_cam_to_body, the function nested at Train_model_pipeline.py:1098-1108), backed by dfepe_pose_chain and
+dfepe_snippet_errors (include/dfepe.h).
+
+Two surfaces:
+
+  * Exp_table_processor keeps the reference's signatures and return types: numpy in, numpy out (float64, the errors float32, the
+    dict keys errors / scale_factors / aligned_poses, `assert len(est) <= len(gt)`, the last window never scored).  The inputs
+    go to the current GPU, the kernels run, the results come back -- a drop-in for notebooks/exp_process_table.ipynb.
+  * odometry_summary takes val_rt_batch's device Rt_cam and stays on the device: camera-to-body, trajectory, snippet errors and
+    their mean / std in two launches, without a host synchronisation, capturable in a hipGraph.
+
+Differences from the reference, all documented where they arise: everything is computed in float64 (the reference compensates a
+float32 ground truth in float32 arithmetic because numpy.stack keeps the dtype; here it is widened first); compute_pose_error and
+pose_seq_ate take snippets of at most 64 poses (the reference's use is 5); the stand-alone compute_pose_error returns ATE and RE
+as float64 scalars that carry float32 precision (the kernel's error array is float32, as pose_seq_ate's is).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+
+Tensor = torch.Tensor
+
+
+def _dev():
+    if not torch.cuda.is_available():
+        raise _lib.DfepeError("the odometry evaluation runs on the GPU (this package has no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to_dev(poses) -> Tensor:
+    """numpy / list of [3,4] or [4,4] poses -> float64 [n,3,4] on the current GPU"""
+    a = np.stack([np.asarray(p, dtype=np.float64) for p in poses]) if len(poses) else np.zeros((0, 3, 4))
+    if a.ndim != 3 or a.shape[1] not in (3, 4) or a.shape[2] != 4:
+        raise ValueError(f"poses must be [n,3,4] or [n,4,4], got {a.shape}")
+    return torch.from_numpy(np.ascontiguousarray(a[:, :3])).to(_dev())
+
+
+def relative_pose_cam_to_body(relative_scene_pose, Rt_cam2_gt):
+    """transform the camera pose from camera coordinate to body coordinate: inv(Rt_cam2_gt) @ relative_scene_pose @ Rt_cam2_gt
+    on 4x4 host matrices, as the reference's nested function (Train_model_pipeline.py:1098-1108).  This per-pair host helper
+    is the reference's own expression; on the device the same step is the cam2body argument of ops.pose_chain /
+    odometry_summary, where it is folded into the chain kernel."""
+    return np.linalg.inv(Rt_cam2_gt) @ relative_scene_pose @ Rt_cam2_gt
+
+
+class Exp_table_processor:
+    """The four odometry methods of the reference's Exp_table_processor (the rest of that class reads and tabulates files)."""
+
+    @staticmethod
+    def compensate_poses(poses):
+        """poses np[batch, 3, 4] -> np[batch, 3, 4] float64: the first pose's translation subtracted from every translation,
+        then every pose multiplied from the left by the inverse of the first pose's 3x3.  Any batch length: longer ones go
+        through the kernel 63 poses at a time behind a copy of the first pose."""
+        P = _to_dev(poses)
+        n, K = P.shape[0], _lib.SNIPPET_MAX_L
+        if n == 0:
+            raise ValueError("compensate_poses needs at least one pose")
+        if n <= K:
+            r = ops.snippet_errors(P[None], P[None], seq_length=n, windows=[1], want_compensated=True)
+            return r["compensated"][0, 0].cpu().numpy()
+        rest = P[1:]
+        pad = (-len(rest)) % (K - 1)
+        rest = torch.cat([rest, P[:1].expand(pad, 3, 4)]).view(-1, K - 1, 3, 4)
+        batch = torch.cat([P[:1].expand(len(rest), 1, 3, 4), rest], dim=1).contiguous()
+        c = ops.snippet_errors(batch, batch, seq_length=K, windows=[1] * len(batch), want_compensated=True)["compensated"][:, 0]
+        return torch.cat([c[0, :1], c[:, 1:].reshape(-1, 3, 4)])[:n].cpu().numpy()
+
+    @staticmethod
+    def get_abs_poses(poses, if_print=False):
+        """poses: iterable of 4x4 relative poses -> np[n+1, 3, 4] float64, the identity first, then inv(P_k ... P_1)[:3]."""
+        poses = list(poses)
+        out = ops.pose_chain(_to_dev(poses)[None])[0].cpu().numpy()
+        if if_print:
+            for p in out[1:6]:
+                print(f"pose abs: {p}")
+        return out
+
+    @staticmethod
+    def compute_pose_error(gt, pred):
+        """gt, pred np[L, 3, 4], L <= 64 -> {"ATE", "RE", "scale_factor"} (numpy float64 scalars), the poses scored as given.
+        The parameter names are the reference's; pose_seq_ate passes the ESTIMATE as `gt` and the ground truth as `pred`."""
+        a, b = _to_dev(gt), _to_dev(pred)
+        if a.shape != b.shape:
+            raise ValueError(f"gt and pred must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        L = a.shape[0]
+        r = ops.snippet_errors(a[None], b[None], seq_length=L, windows=[1], compensate=False)
+        # the kernel's error array is float32 (pose_seq_ate's): ATE and RE are returned as float64 scalars, as the reference's
+        # are, but carry float32 precision; the scale factor is the full float64
+        e = r["errors"][0, 0].double().cpu().numpy()
+        return {"ATE": np.float64(e[0]), "RE": np.float64(e[1]), "scale_factor": np.float64(r["scale_factors"][0, 0].item())}
+
+    @staticmethod
+    def pose_seq_ate(est_poses, gt_poses, seq_length=5):
+        """compute absolute translation error on small snippets: est_poses np[N, 3, 4], gt_poses np[>= N, 3, 4] ->
+        {"errors": np[N - seq_length, 2] float32 (ATE, RE), "scale_factors": list of float64, "aligned_poses": list of np[3, 4]}.
+        As in the reference the last window (start N - seq_length) is not scored, and the mean / std are printed."""
+        assert len(est_poses) <= len(gt_poses)
+        est_length = len(est_poses) - seq_length
+        if est_length < 0:
+            raise ValueError("negative dimensions are not allowed")  # the reference's numpy.zeros((est_length, 2))
+        E = _to_dev(est_poses)
+        G = _to_dev(gt_poses[:len(est_poses)])
+        r = ops.snippet_errors(E[None], G[None], seq_length=seq_length, windows=[est_length])
+        errors = r["errors"][0].cpu().numpy()
+        scale = r["scale_factors"][0].cpu().numpy()
+        aligned = r["aligned_poses"][0].cpu().numpy()
+        with np.errstate(all="ignore"):
+            mean_errors, std_errors = (errors.mean(0), errors.std(0)) if len(errors) else (np.full(2, np.nan), np.full(2, np.nan))
+        print("")
+        print("Results")
+        print("\t {:>10}, {:>10}".format("ATE", "RE"))
+        print("mean \t {:10.4f}, {:10.4f}".format(*mean_errors))
+        print("std \t {:10.4f}, {:10.4f}".format(*std_errors))
+        return {"errors": errors, "scale_factors": [s for s in scale], "aligned_poses": [p for p in aligned]}
+
+
+def _rows3(t: Tensor) -> Tensor:
+    return t[..., :3, :] if t.shape[-2] == 4 else t
+
+
+def odometry_summary(Rt_cam: Tensor, Rt_cam2_gt, gt_poses: Tensor, seq_length: int = 5, lengths=None) -> dict:
+    """From val_rt_batch's camera motions to the reported odometry metric, on the device.
+      Rt_cam      [n,3,4] (one sequence, val_rt_batch's "Rt_cam") or [S,n,3,4] (a padded batch of sequences)
+      Rt_cam2_gt  the samples' camera-to-body transforms, [.., 3 or 4, 4]: one per pose ([n,..] / [S,n,..]) or one per
+                  sequence ([..] / [S,..]); None scores the camera motions as they are
+      gt_poses    [n+1,3,4] / [S,n+1,3,4] ground-truth absolute poses (any float dtype; widened to float64)
+      lengths     [S] relative poses per sequence of a padded batch (host values or a device tensor), default n
+    -> dict of device tensors: abs_poses [S,n+1,3,4], errors [S,W,2] float32 with W = n + 1 - seq_length (the reference never
+    scores the last window), scale_factors [S,W], aligned_poses [S,W,3,4], ATE_mean, ATE_std, RE_mean, RE_std [S] float64;
+    without the leading S for a single sequence.  Rows past a sequence's own windows are zero.  Two launches, no host
+    synchronisation (with lengths on the host they are uploaded; inside a graph capture pass a device tensor or None)."""
+    single = Rt_cam.dim() == 3
+    rel = Rt_cam[None] if single else Rt_cam
+    gt = gt_poses[None] if single else gt_poses
+    S, n = rel.shape[0], rel.shape[1]
+    c = None
+    if Rt_cam2_gt is not None:
+        c = _rows3(Rt_cam2_gt)
+        if single:
+            c = c[None]
+    abs_poses = ops.pose_chain(rel, lengths=lengths, cam2body=c)
+    W = max(n + 1 - seq_length, 0)
+    if lengths is None:
+        windows = torch.full((S,), W, dtype=torch.int32, device=rel.device)  # filled on the device: no upload, no wait
+    elif isinstance(lengths, Tensor) and lengths.is_cuda:
+        windows = (lengths.to(torch.int32) + (1 - seq_length)).clamp_(min=0)
+    else:
+        host = lengths.tolist() if isinstance(lengths, Tensor) else list(lengths)
+        windows = [max(int(v) + 1 - seq_length, 0) for v in host]
+    r = ops.snippet_errors(abs_poses, gt, seq_length=seq_length, windows=windows, capacity=W)
+    st = r["stats"]
+    out = {"abs_poses": abs_poses, "errors": r["errors"], "scale_factors": r["scale_factors"], "aligned_poses": r["aligned_poses"],
+           "ATE_mean": st[:, 0], "ATE_std": st[:, 1], "RE_mean": st[:, 2], "RE_std": st[:, 3]}
+    return {k: v[0] for k, v in out.items()} if single else out

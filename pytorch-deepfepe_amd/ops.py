@@ -1085,6 +1085,106 @@ def correct_matches(F: Tensor, pts1: Tensor, pts2: Tensor, want_cost: bool = Fal
 
 
 # ------------------------------------------------------------------------------------------------
+# odometry evaluation: pose chain and snippet ATE / RE (deepFEPE/utils/eval_tools.py:252-375)
+# ------------------------------------------------------------------------------------------------
+def _pose12(t: Tensor, name: str, lead: int) -> Tensor:
+    """[..., 3, 4] or [..., 12] with `lead` leading dimensions -> contiguous float64 [..., 12] on the GPU."""
+    if not t.is_cuda:
+        raise _lib.DfepeError(f"{name} must live on the GPU (this package has no CPU path)")
+    t = t.detach().to(torch.float64)
+    if t.dim() == lead + 2:
+        if tuple(t.shape[-2:]) != (3, 4):
+            raise ValueError(f"{name}: poses are 3x4 (or 12 numbers, row-major), got {tuple(t.shape)}")
+        t = t.reshape(*t.shape[:-2], 12)
+    if t.dim() != lead + 1 or t.shape[-1] != 12:
+        raise ValueError(f"{name}: expected {lead} leading dimension(s) and 3x4 poses, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _lengths_arg(lengths, S: int, hi: int, dev, name: str):
+    """lengths as a device int32 [S] -- and, when they are host values, checked against [0, hi] here (a device tensor cannot be
+    checked without a synchronisation: its range is the caller's contract, and the kernels clamp it to their buffers)."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, Tensor) and lengths.is_cuda:
+        _shape(lengths, name, S)
+        return lengths.to(torch.int32).contiguous()
+    host = [int(v) for v in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
+    if len(host) != S or any(v < 0 or v > hi for v in host):
+        raise ValueError(f"{name} must be {S} values in [0, {hi}], got {host}")
+    return torch.tensor(host, dtype=torch.int32, device=dev)
+
+
+def pose_chain(rel: Tensor, lengths=None, cam2body: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Relative poses -> trajectory, Exp_table_processor.get_abs_poses for a batch of sequences: rel [S,n,3,4] (or [S,n,12])
+    -> abs [S,n+1,3,4] float64 with abs[s,0] the identity and abs[s,k] = inv(P_k ... P_1) (general inverse).  cam2body
+    [S,3,4] (one per sequence) or [S,n,3,4] (one per pose): P_k is first taken to body coordinates, inv(C) P_k C
+    (relative_pose_cam_to_body).  lengths [S] (host values or a device tensor) for a padded batch: entries past lengths[s]
+    are not written (they keep what `out` held; without `out` they are zero).  One launch, no host synchronisation."""
+    r = _pose12(rel, "rel", 2)
+    S, n = r.shape[0], r.shape[1]
+    dev = r.device
+    c, stride = None, 0
+    if cam2body is not None:
+        if cam2body.dim() == 2 or (cam2body.dim() == 3 and cam2body.shape[-1] == 4):  # [S,12] or [S,3,4]: one per sequence
+            c = _pose12(cam2body, "cam2body", 1)
+            _shape(c, "cam2body", S, 12)
+        else:
+            c, stride = _pose12(cam2body, "cam2body", 2), 12
+            _shape(c, "cam2body", S, n, 12)
+    ln = _lengths_arg(lengths, S, n, dev, "lengths")
+    if out is None:
+        out = torch.zeros(S, n + 1, 12, device=dev, dtype=torch.float64) if ln is not None else \
+            torch.empty(S, n + 1, 12, device=dev, dtype=torch.float64)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != S * (n + 1) * 12 or out.device != dev:
+        raise ValueError("out must be a contiguous float64 tensor of S (n + 1) 12 elements on rel's device")
+    with _on(dev):
+        rc = _lib.lib().dfepe_pose_chain(_stream(), _ptr(r), _ptr(ln), _ptr(c), stride, S, n, _ptr(out))
+    _lib.check(rc, "dfepe_pose_chain")
+    return out.view(S, n + 1, 3, 4)
+
+
+def snippet_errors(est: Tensor, gt: Tensor, seq_length: int = 5, windows=None, compensate: bool = True,
+                   want_compensated: bool = False, capacity: Optional[int] = None) -> dict:
+    """The snippet ATE / RE of Exp_table_processor.pose_seq_ate for a batch of trajectories: est, gt [S,m,3,4] (or [S,m,12])
+    absolute poses; window w of a sequence covers poses w .. w + seq_length - 1.  windows [S] (host values, checked here, or a
+    device tensor, the caller's contract: windows[s] + seq_length - 1 <= the sequence's number of poses): how many windows each
+    sequence has; default m - seq_length, the reference's count (it never scores the last window).  capacity: rows in the
+    outputs (default: the largest host value of windows, or m - seq_length + 1 for a device tensor).
+    compensate=False scores the poses as given (a stand-alone compute_pose_error).
+    -> dict: errors [S,W,2] float32 (ATE, RE), scale_factors [S,W] float64, aligned_poses [S,W,3,4] float64, stats [S,4] float64
+    (ATE mean, ATE std, RE mean, RE std; NaN without windows), with want_compensated also compensated [S,W,L,3,4] (the
+    estimate's snippets after compensate_poses).  Rows past windows[s] are zero.  One launch, no host synchronisation."""
+    L = int(seq_length)
+    if not 1 <= L <= _lib.SNIPPET_MAX_L:
+        raise _lib.DfepeError(f"seq_length must be in [1, {_lib.SNIPPET_MAX_L}], got {L}")
+    e, g = _pose12(est, "est", 2), _pose12(gt, "gt", 2)
+    S, m = e.shape[0], e.shape[1]
+    _shape(g, "gt", S, m, 12)
+    dev = e.device
+    most = max(m - L + 1, 0)
+    if windows is None:
+        windows = [max(m - L, 0)] * S
+    wn = _lengths_arg(windows, S, most, dev, "windows")
+    if capacity is None:
+        capacity = most if isinstance(windows, Tensor) and windows.is_cuda else max([int(v) for v in windows], default=0)
+    W = int(capacity)
+    errors = torch.zeros(S, W, 2, device=dev, dtype=torch.float32)
+    scale = torch.zeros(S, W, device=dev, dtype=torch.float64)
+    aligned = torch.zeros(S, W, 12, device=dev, dtype=torch.float64)
+    comp = torch.zeros(S, W, L, 12, device=dev, dtype=torch.float64) if want_compensated else None
+    stats = torch.empty(S, 4, device=dev, dtype=torch.float64)
+    with _on(dev):
+        rc = _lib.lib().dfepe_snippet_errors(_stream(), _ptr(e), _ptr(g), _ptr(wn), S, m, W, L, 0 if compensate else 1,
+                                             _ptr(errors), _ptr(scale), _ptr(aligned), _ptr(comp), _ptr(stats))
+    _lib.check(rc, "dfepe_snippet_errors")
+    out = {"errors": errors, "scale_factors": scale, "aligned_poses": aligned.view(S, W, 3, 4), "stats": stats}
+    if want_compensated:
+        out["compensated"] = comp.view(S, W, L, 3, 4)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # validation summary reductions ("next" row f-2)
 # ------------------------------------------------------------------------------------------------
 METRIC_THS = (0.0, 0.01, 0.03, 0.05, 0.1, 0.3, 0.5, 1.0, 2.0, 5.0, 10.0, 90.0, 180.0)
