@@ -807,6 +807,63 @@ int dfepe_pose_chain(void *stream, const double *rel, const int *lengths, const 
 int dfepe_snippet_errors(void *stream, const double *est, const double *gt, const int *windows, int S, int m_max, int W, int L,
                          int no_compensate, float *errors, double *scale, double *aligned, double *compensated, double *stats);
 
+/*
+ * KITTI odometry table, part 1: first-frame re-basing and trajectory alignment (the published KITTI devkit / kitti-odom-eval
+ * evaluation, steps 1 and 2).  fp64 throughout; poses as in dfepe_pose_chain.
+ *   est, gt [S,n_max,12] absolute poses; est_len, gt_len [S] int32 or NULL (n_max).  n = gt_len clamped to [0, n_max] and
+ *     m = est_len clamped to [0, n]: frame i of the estimate belongs to frame i of the ground truth, and nothing is read or written
+ *     past m resp. n.
+ *   Every pose is re-based on its trajectory's first one, inv(P_0) P_i (general inverse).  Then, with x the estimate's and y the
+ *   ground truth's translations over the m common frames, mode is
+ *     DFEPE_TRAJ_NONE        nothing more;
+ *     DFEPE_TRAJ_SCALE       c = sum x.y / sum x.x, the estimate's translations times c;
+ *     DFEPE_TRAJ_SCALE_7DOF, DFEPE_TRAJ_7DOF, DFEPE_TRAJ_6DOF   Umeyama: means, sigma_x^2 = (1/m) sum |x - mx|^2 and
+ *       C = (1/m) sum (y - my)(x - mx)^T in two passes (means first, then centred sums), C = U D V^T (3x3 one-sided Jacobi),
+ *       S = diag(1, 1, -1) when det(U) det(V^T) < 0, r = U S V^T, c = tr(D S) / sigma_x^2 (1 for 6DOF), t = my - c r mx.
+ *       SCALE_7DOF multiplies the estimate's translations by c only; 7DOF and 6DOF multiply them by c and then every pose from the
+ *       left by [r | t].  sigma_x^2 = 0 gives the IEEE result of the formula (inf or NaN), which propagates.  A planar trajectory
+ *       (C of rank 2) is decided: the column of U of the smallest singular value is the cross product of the other two.  A
+ *       collinear trajectory leaves r and t undetermined (NaN or no rotation); c, and with it SCALE_7DOF, is still decided.
+ *   est_out, gt_out [S,n_max,12]: the aligned estimate (m poses) and the re-based ground truth (n poses); not the inputs' memory.
+ *   rtc [S,13]: r (9, row-major), t (3), c; the identity, 0 and 1 where a mode does not compute them (and for m = 0).
+ *   S < 0, n_max < 0 or an unknown mode: INVALID_ARG; S == 0 returns 0 before any launch; then a NULL rtc, or with n_max > 0 a NULL
+ *   est, gt, est_out or gt_out, is INVALID_ARG; n_max >= 2^31 / 12 - 1: UNSUPPORTED.
+ * One workgroup of 256 lanes per sequence; every sum is a fixed tree (a lane's frames ascending, a butterfly across the wavefront,
+ * the wavefront totals in order).  No atomics: the same bits on every run.  Contraction is off (csrc/odometry_math.h says why).
+ */
+#define DFEPE_TRAJ_NONE 0
+#define DFEPE_TRAJ_SCALE 1
+#define DFEPE_TRAJ_SCALE_7DOF 2
+#define DFEPE_TRAJ_7DOF 3
+#define DFEPE_TRAJ_6DOF 4
+int dfepe_trajectory_align(void *stream, const double *est, const double *gt, const int *est_len, const int *gt_len, int S, int n_max,
+                           int mode, double *est_out, double *gt_out, double *rtc);
+
+/*
+ * KITTI odometry table, part 2: segment errors, ATE and RPE of aligned trajectories (steps 3 to 5 of the same evaluation).
+ *   est, gt [S,n_max,12], est_len, gt_len: as above (the outputs of dfepe_trajectory_align).
+ *   dist [S,n_max] fp64: written; dist[i] = the ground truth's path length up to frame i.
+ *   For first = 0, step, 2 step, ... < n and len = 100, 200, .. 800: last = the first i >= first with dist[i] > dist[first] + len,
+ *   found by bisection; the pair is scored unless there is no such i, or last >= m, or first >= m.  (dist is a parallel scan:
+ *   where the ground truth stands still dist[i + 1] can round a few last places below dist[i], and the bisection can then place
+ *   last differently from a linear search only where dist is within that rounding of dist[first] + len.)  With
+ *   E = inv(inv(est_first) est_last) (inv(gt_first) gt_last), r = arccos(clamp((tr E_R - 1) / 2, -1, 1)), t = |E_t|:
+ *   rows [S,F,8,5] fp64: [first, r / len, t / len, len, len / (0.1 (last - first + 1))], zeros for a pair that is not scored;
+ *   valid [S,F,8] bytes: 1 scored, 0 not; F >= ceil(n_max / step), so that the rows hold every first frame (fewer: INVALID_ARG);
+ *   rows of first frames >= n are not written.  count [S] int32: scored pairs.
+ *   summary [S,5] fp64: t_rel = 100 mean(t / len) in %, r_rel = mean(r / len) 180 / pi 100 in deg / 100 m (both 0 without a scored
+ *   pair, as the devkit), ATE = sqrt(mean_i |gt_xyz,i - est_xyz,i|^2) over the m frames (NaN for m = 0), and the RPE over i < m - 1
+ *   with E = inv(inv(gt_i) gt_i+1) (inv(est_i) est_i+1): mean |E_t| in m and mean angle in degrees (NaN for m <= 1).
+ *   S < 0, n_max < 0, step < 1, F < 0: INVALID_ARG; S == 0 returns 0 before any launch; then NULL count or summary, with n_max > 0
+ *   NULL est, gt or dist, with F > 0 NULL rows or valid, are INVALID_ARG; n_max >= 2^31 / 12 - 1 or F > (2^31 - 1) / 40: UNSUPPORTED;
+ *   then F step < n_max: INVALID_ARG.
+ * One workgroup per sequence: a shuffle-and-LDS scan for dist (kept in LDS up to 4096 frames, read from `dist` beyond), one lane per
+ * (first, len) pair, lanes striding the frames for ATE and RPE, one fixed-order reduction.  No atomics; the same bits on every run.
+ */
+int dfepe_kitti_odometry_errors(void *stream, const double *est, const double *gt, const int *est_len, const int *gt_len, int S,
+                                int n_max, int step, int F, double *dist, double *rows, unsigned char *valid, int *count,
+                                double *summary);
+
 #ifdef __cplusplus
 }
 #endif

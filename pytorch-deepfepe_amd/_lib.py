@@ -29,6 +29,8 @@ RANSAC_MIN_N = 15  # dfepe_ransac_fundamental: below, OpenCV switches to LMedS (
 POSE_CHAIN_THREADS = 256  # dfepe_pose_chain: lanes per sequence (kChainThreads, csrc/odometry.hip)
 POSE_CHAIN_CHUNK = 8  # ... and consecutive poses per lane and tile (kChainChunk): a tile is 2048 poses
 SNIPPET_MAX_L = 64  # dfepe_snippet_errors: longest snippet (kSnipMaxL)
+TRAJ_MODES = ("none", "scale", "scale_7dof", "7dof", "6dof")  # dfepe_trajectory_align: mode = index (DFEPE_TRAJ_*, traj::Mode)
+KITTI_DIST_LDS = 4096  # dfepe_kitti_odometry_errors: frames whose path length stays in LDS (kDistLds, csrc/trajectory.hip)
 RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked models of the one sample (not built)
 
 _P = c_void_p
@@ -113,6 +115,8 @@ _SIGNATURES = {
     "dfepe_correct_matches": (c_int, [_P, _P, c_long, _P, _P, c_int, c_int, _P, _P, _P]),
     "dfepe_pose_chain": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P]),
     "dfepe_snippet_errors": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dfepe_trajectory_align": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "dfepe_kitti_odometry_errors": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -1,7 +1,8 @@
 """Mirror of the odometry evaluation of deepFEPE/utils/eval_tools.py (Exp_table_processor: compensate_poses :252-265,
 get_abs_poses :268-284, compute_pose_error :309-331, pose_seq_ate :334-375) and of the camera-to-body step in front of it
 (relative_pose_cam_to_body, the function nested at Train_model_pipeline.py:1098-1108), backed by dfepe_pose_chain and
-dfepe_snippet_errors (include/dfepe.h).
+dfepe_snippet_errors (include/dfepe.h); and the step the reference leaves to an external tool, the KITTI odometry table
+(kitti_odometry_eval, odometry_table, read_kitti_poses, write_kitti_result at the end of this file).
 
 Two surfaces:
 
@@ -17,6 +18,8 @@ pose_seq_ate take snippets of at most 64 poses (the reference's use is 5); the s
 as float64 scalars that carry float32 precision (the kernel's error array is float32, as pose_seq_ate's is).
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -157,3 +160,106 @@ def odometry_summary(Rt_cam: Tensor, Rt_cam2_gt, gt_poses: Tensor, seq_length: i
     out = {"abs_poses": abs_poses, "errors": r["errors"], "scale_factors": r["scale_factors"], "aligned_poses": r["aligned_poses"],
            "ATE_mean": st[:, 0], "ATE_std": st[:, 1], "RE_mean": st[:, 2], "RE_std": st[:, 3]}
     return {k: v[0] for k, v in out.items()} if single else out
+
+
+# ---- the KITTI odometry table (README "Evaluate visual odometry", step 3: kitti-odom-eval) ---------------------------------------
+# The reference exports the absolute poses and hands them to the kitti-odom-eval tool, whose five numbers per sequence are what it
+# publishes (results/*/result.txt).  The functions below are that step on the device: dfepe_trajectory_align and
+# dfepe_kitti_odometry_errors (include/dfepe.h) behind ops.trajectory_align / ops.kitti_odometry_errors.
+KITTI_RESULT_LINES = ("Trans. err. (%)", "Rot. err. (deg/100m)", "ATE (m)", "RPE (m)", "RPE (deg)")
+
+
+def _table(est: Tensor, gt: Tensor, alignment: str, step: int, est_lengths, gt_lengths) -> dict:
+    if est_lengths is None and est.shape[1] < gt.shape[1]:
+        # trajectory_align returns the estimate padded to the ground truth's frames: the second launch must be told its length too
+        est_lengths = torch.full((est.shape[0],), est.shape[1], dtype=torch.int32, device=gt.device)
+    al = ops.trajectory_align(est, gt, alignment, est_lengths=est_lengths, gt_lengths=gt_lengths)
+    r = ops.kitti_odometry_errors(al["est"], al["gt"], step=step, est_lengths=est_lengths, gt_lengths=gt_lengths)
+    sm = r["summary"]
+    return {"t_rel": sm[:, 0], "r_rel": sm[:, 1], "ATE": sm[:, 2], "RPE_trans": sm[:, 3], "RPE_rot": sm[:, 4], "summary": sm,
+            "segments": r["rows"], "valid": r["valid"], "count": r["count"], "dist": r["dist"], "aligned_poses": al["est"],
+            "gt_poses": al["gt"], "r": al["r"], "t": al["t"], "scale": al["c"]}
+
+
+def kitti_odometry_eval(est_abs, gt_abs, alignment: str = "scale_7dof", step: int = 10, lengths=None) -> dict:
+    """The kitti-odom-eval numbers of one sequence ([m,3,4] estimate, [n,3,4] ground truth, m <= n) or of a padded batch
+    ([S,m,3,4], [S,n,3,4]; lengths = (est_lengths, gt_lengths), each [S] or None), on host arrays or device tensors.
+    alignment: "none", "scale", "scale_7dof" (the default, and the mode that reproduces the reference's published numbers),
+    "7dof" or "6dof"; step: the distance between first frames of the segments (the devkit's 10).
+    -> dict: t_rel (%), r_rel (deg / 100 m), ATE (m), RPE_trans (m), RPE_rot (deg), summary (the five in that order), segments
+    [F,8,5] rows [first, r_err, t_err, len, speed], valid [F,8], count, dist, aligned_poses, gt_poses, r, t, scale.  Device tensors
+    in give device tensors out, without a host synchronisation; host arrays in give numpy arrays (and python floats / an int for
+    the scalars of a single sequence) out."""
+    host = not isinstance(est_abs, Tensor)
+    est = torch.as_tensor(np.asarray(est_abs, np.float64)).to(_dev()) if host else est_abs
+    gt = torch.as_tensor(np.asarray(gt_abs, np.float64)).to(_dev()) if not isinstance(gt_abs, Tensor) else gt_abs
+    est, gt = _rows3(est), _rows3(gt)
+    single = est.dim() == 3
+    if single:
+        est, gt = est[None], gt[None]
+    el, gl = lengths if lengths is not None else (None, None)
+    out = _table(est, gt, alignment, step, el, gl)
+    if single:
+        out = {k: v[0] for k, v in out.items()}
+    if host:
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        if single:
+            out = {k: (v.item() if v.ndim == 0 else v) for k, v in out.items()}
+    return out
+
+
+def odometry_table(Rt_cam: Tensor, Rt_cam2_gt, gt_poses: Tensor, alignment: str = "scale_7dof", step: int = 10, lengths=None) -> dict:
+    """From val_rt_batch's camera motions to the KITTI odometry table, on the device: ops.pose_chain (with the camera-to-body
+    conjugation), then the two launches of kitti_odometry_eval.  Rt_cam, Rt_cam2_gt, gt_poses and lengths (relative poses per
+    sequence) as in odometry_summary; -> kitti_odometry_eval's dict plus abs_poses, without the leading S for a single sequence.
+    Three launches, no host synchronisation (inside a graph capture pass lengths as a device tensor or None)."""
+    single = Rt_cam.dim() == 3
+    rel = Rt_cam[None] if single else Rt_cam
+    gt = _rows3(gt_poses[None] if single else gt_poses)
+    c = None
+    if Rt_cam2_gt is not None:
+        c = _rows3(Rt_cam2_gt)
+        if single:
+            c = c[None]
+    abs_poses = ops.pose_chain(rel, lengths=lengths, cam2body=c)
+    frames = None
+    if lengths is not None:
+        if isinstance(lengths, Tensor) and lengths.is_cuda:
+            frames = lengths.to(torch.int32) + 1
+        else:
+            frames = [int(v) + 1 for v in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
+    out = _table(abs_poses, gt, alignment, step, frames, frames)
+    out["abs_poses"] = abs_poses
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
+def read_kitti_poses(path) -> np.ndarray:
+    """A KITTI pose file (one 3x4 pose, 12 numbers, per line) -> np[n,3,4] float64."""
+    a = np.loadtxt(path, dtype=np.float64, ndmin=2)
+    if a.shape[1] != 12:
+        raise ValueError(f"{path}: expected 12 numbers per line, got {a.shape[1]}")
+    return a.reshape(-1, 3, 4)
+
+
+def write_kitti_result(out_dir, seq, result) -> None:
+    """Write kitti_odometry_eval's result of one sequence in the layout of the reference's shipped results: <out_dir>/result.txt
+    with the five numbers (three decimals) and <out_dir>/errors/<seq>.txt with one row `first_frame r_err t_err len speed` per
+    scored segment.  seq: the sequence number or its two-digit name."""
+    def val(k):
+        return float(result[k].item() if hasattr(result[k], "item") else result[k])
+
+    name = f"{int(seq):02d}"
+    rows = result["segments"]
+    valid = result["valid"]
+    if isinstance(rows, Tensor):
+        rows, valid = rows.cpu().numpy(), valid.cpu().numpy()
+    rows = np.asarray(rows, np.float64).reshape(-1, 5)[np.asarray(valid, bool).reshape(-1)]
+    os.makedirs(os.path.join(out_dir, "errors"), exist_ok=True)
+    with open(os.path.join(out_dir, "errors", name + ".txt"), "w") as f:
+        for r in rows:
+            f.write(f"{int(r[0])} {float(r[1])!r} {float(r[2])!r} {int(r[3])} {float(r[4])!r}\n")
+    with open(os.path.join(out_dir, "result.txt"), "w") as f:
+        f.write(f"Sequence: \t {int(seq)} \n")
+        for label, key in zip(KITTI_RESULT_LINES, ("t_rel", "r_rel", "ATE", "RPE_trans", "RPE_rot")):
+            f.write(f"{label}: \t {val(key):.3f} \n")
+        f.write("\n")

@@ -1185,6 +1185,71 @@ def snippet_errors(est: Tensor, gt: Tensor, seq_length: int = 5, windows=None, c
 
 
 # ------------------------------------------------------------------------------------------------
+# KITTI odometry table: alignment, segment errors, ATE, RPE (the KITTI devkit / kitti-odom-eval evaluation)
+# ------------------------------------------------------------------------------------------------
+def _traj_args(est: Tensor, gt: Tensor, est_lengths, gt_lengths):
+    e, g = _pose12(est, "est", 2), _pose12(gt, "gt", 2)
+    S, n = g.shape[0], g.shape[1]
+    if e.shape[0] != S or e.shape[1] > n:
+        raise ValueError(f"est must have gt's batch and at most its frames, got {tuple(e.shape)} against {tuple(g.shape)}")
+    dev = g.device
+    m = e.shape[1]
+    if m < n:  # the kernels take one n_max: the estimate is padded and its length says so
+        e = torch.cat([e, torch.zeros(S, n - m, 12, device=dev, dtype=torch.float64)], dim=1)
+        if est_lengths is None:
+            est_lengths = torch.full((S,), m, dtype=torch.int32, device=dev)
+    return e, g, S, n, _lengths_arg(est_lengths, S, m, dev, "est_lengths"), _lengths_arg(gt_lengths, S, n, dev, "gt_lengths")
+
+
+def trajectory_align(est: Tensor, gt: Tensor, mode: str = "scale_7dof", est_lengths=None, gt_lengths=None) -> dict:
+    """Steps 1 and 2 of the KITTI odometry evaluation for a batch of sequences: est [S,m,3,4], gt [S,n,3,4] (or [..,12]) absolute
+    poses, m <= n, frame i of one corresponding to frame i of the other; est_lengths, gt_lengths [S] (host values, checked here,
+    or device tensors, clamped by the kernel) for padded batches.  Both trajectories are re-based on their first pose; mode is
+    one of _lib.TRAJ_MODES: "none", "scale" (least-squares scale of the translations), "scale_7dof" (Umeyama's scale only),
+    "7dof", "6dof" (Umeyama's similarity / rigid transform applied to every pose).
+    -> dict: est [S,n,3,4] (aligned; zero past a sequence's m), gt [S,n,3,4] (re-based; zero past its n), r [S,3,3], t [S,3],
+    c [S] float64.  One launch, no host synchronisation."""
+    if mode not in _lib.TRAJ_MODES:
+        raise ValueError(f"mode must be one of {_lib.TRAJ_MODES}, got {mode!r}")
+    e, g, S, n, el, gl = _traj_args(est, gt, est_lengths, gt_lengths)
+    dev = g.device
+    eo = torch.zeros(S, n, 12, device=dev, dtype=torch.float64)
+    go = torch.zeros(S, n, 12, device=dev, dtype=torch.float64)
+    rtc = torch.empty(S, 13, device=dev, dtype=torch.float64)
+    with _on(dev):
+        rc = _lib.lib().dfepe_trajectory_align(_stream(), _ptr(e), _ptr(g), _ptr(el), _ptr(gl), S, n, _lib.TRAJ_MODES.index(mode),
+                                               _ptr(eo), _ptr(go), _ptr(rtc))
+    _lib.check(rc, "dfepe_trajectory_align")
+    return {"est": eo.view(S, n, 3, 4), "gt": go.view(S, n, 3, 4), "r": rtc[:, :9].reshape(S, 3, 3), "t": rtc[:, 9:12], "c": rtc[:, 12]}
+
+
+def kitti_odometry_errors(est: Tensor, gt: Tensor, step: int = 10, est_lengths=None, gt_lengths=None) -> dict:
+    """Steps 3 to 5 of the KITTI odometry evaluation on aligned trajectories (trajectory_align's est and gt): est [S,m,3,4],
+    gt [S,n,3,4], lengths as there (trajectory_align returns a shorter estimate padded to n frames: its length goes in est_lengths
+    here, as compat.eval_tools does).  For every first frame 0, step, 2 step, ... and every length 100 .. 800 m the segment's
+    rotation and translation error per metre, then the whole-trajectory ATE and the RPE.
+    -> dict: rows [S,F,8,5] float64 with F = ceil(n / step): [first, r_err, t_err, len, speed] (zero where not valid), valid
+    [S,F,8] bool, count [S] int32, summary [S,5] float64: t_rel (%), r_rel (deg / 100 m), ATE (m), RPE (m), RPE (deg), and dist
+    [S,n] float64, the ground truth's path length.  One launch, no host synchronisation."""
+    step = int(step)
+    if step < 1:
+        raise ValueError(f"step must be at least 1, got {step}")
+    e, g, S, n, el, gl = _traj_args(est, gt, est_lengths, gt_lengths)
+    dev = g.device
+    F = (n + step - 1) // step
+    dist = torch.zeros(S, n, device=dev, dtype=torch.float64)
+    rows = torch.zeros(S, F, 8, 5, device=dev, dtype=torch.float64)
+    valid = torch.zeros(S, F, 8, device=dev, dtype=torch.uint8)
+    count = torch.empty(S, device=dev, dtype=torch.int32)
+    summary = torch.empty(S, 5, device=dev, dtype=torch.float64)
+    with _on(dev):
+        rc = _lib.lib().dfepe_kitti_odometry_errors(_stream(), _ptr(e), _ptr(g), _ptr(el), _ptr(gl), S, n, step, F, _ptr(dist),
+                                                    _ptr(rows), _ptr(valid), _ptr(count), _ptr(summary))
+    _lib.check(rc, "dfepe_kitti_odometry_errors")
+    return {"rows": rows, "valid": valid.view(torch.bool), "count": count, "summary": summary, "dist": dist}
+
+
+# ------------------------------------------------------------------------------------------------
 # validation summary reductions ("next" row f-2)
 # ------------------------------------------------------------------------------------------------
 METRIC_THS = (0.0, 0.01, 0.03, 0.05, 0.1, 0.3, 0.5, 1.0, 2.0, 5.0, 10.0, 90.0, 180.0)
