@@ -33,7 +33,9 @@ extern "C" {
 #define DFEPE_ERR_HIP (-2)         /* a HIP runtime call failed (launch, attribute)            */
 #define DFEPE_ERR_UNSUPPORTED (-3) /* valid request this build cannot serve (e.g. N too large) */
 
-/* floats per pair in the `save` buffer handed from dfepe_w8pt_fwd to dfepe_w8pt_bwd */
+/* floats per pair in the `save` buffer handed from dfepe_w8pt_fwd to dfepe_w8pt_bwd.  The record is opaque and never outlives
+   the process that wrote it: its inner layout may differ between builds of the library (csrc/w8pt16_body.h), and a backward that
+   is handed a record of another layout returns NaN gradients instead of misreading it. */
 #define DFEPE_SAVE_FLOATS 128
 
 /* flags for dfepe_w8pt_fwd / dfepe_w8pt_bwd */

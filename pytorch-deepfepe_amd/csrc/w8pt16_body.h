@@ -18,7 +18,8 @@
 //       Householder tridiagonalisation (lane i holds row i of M; broadcasts are row_newbcast DPP moves),
 //       the (skip+1)-th smallest eigenvalue by 16-way multisection on the division-free Sturm sequence (every lane of the
 //       row probes its own shift: a log-spaced round finds the magnitude, ~9 linear rounds of 17x each finish it),
-//       its eigenvector by twisted factorisation, back-transformed through the seven reflectors;
+//       its eigenvector by twisted factorisation, back-transformed by the product Q of the seven reflectors, which is
+//       accumulated as an explicit matrix while tridiagonalising (lane i holds row i) and handed to the backward in the record;
 //     everything is fp64 (full-rate on gfx950), so there is no fp32 sweep to polish and no cluster repair;
 //   * the backward (w8pt16_bwd_pair) applies (M - lam I)^+ through the same tridiagonal form saved here;
 //   * every global load is issued at the top, unconditionally (clamped indices), and every store at the bottom: a load under
@@ -33,25 +34,32 @@
 #include "dfepe_math.h"
 
 // ---- layout of the per-pair `save` record written by w8pt16_fwd_pair (floats; DFEPE_SAVE_FLOATS = 128) ----------
+// The tridiagonalising basis is stored as the explicit orthogonal matrix Q = diag(1, Q') = H_0 H_1 ... H_6 (M / trace M = Q T Q^T),
+// not as its seven reflectors: applying it is then eight independent 8-term sums instead of fourteen dependent broadcast chains.
+// Lane s of the row writes floats 8 s .. 8 s + 7: lane 0 the transforms, lanes 1..8 their own row of Q', lanes 9..15 the rest.
+// f itself is not stored: the backward recomputes f = Q z.  A record never outlives the process that wrote it (it is handed from
+// a forward call to the backward call of the same step), so the layout may change between builds; the two marks below make a
+// backward that is handed anything else poison its output instead of misreading it.
 #define S16_T1 0       // Hartley transform of image 1: s, cx, cy
 #define S16_T2 3       // Hartley transform of image 2
-#define S16_F 6        // 9: the oriented unit eigenvector f (largest-magnitude component positive)
-#define S16_Z 15       // 9: z = H^T f, the eigenvector of the tridiagonal T (same orientation)
-#define S16_HV 26      // 35: reflector k = 0..6, components k+1..8, at offset 8k - k(k-1)/2  (floats 24..63: nothing else, see below)
-#define S16_TD 68      // 9 doubles: diagonal of T  (T = H^T (M / trace M) H)
-#define S16_TE 86      // 8 doubles: off-diagonal of T
-#define S16_LAM 102    // 1 double: the selected eigenvalue of M / trace M
-#define S16_U3 104     // smallest singular triplet of F = reshape(f): u3 (3 floats)
-#define S16_V3 107     //                                              v3 (3 floats)
-#define S16_S3 110     //                                              s3 >= 0
-#define S16_TWIST 111  // twist index of the factorisation (largest-residual-free row), as float
-#define S16_HB 112     // 7: beta_k  (H_k = I - beta_k v_k v_k^T)
-#define S16_INVTR 125  // 1 / trace(M)
-#define S16_SCRATCH 126 // unused since round 3 (kept zero); float 24 takes the branch-free stray stores of the reflector lanes
-#define S16_TAG 127    // record tag: the backward poisons its output when handed anything but a record of this layout
-#define S16_TAG_VALUE 17.0f  // 17: the round-3 layout (TWIST and HB behind S3)
-
-__host__ __device__ constexpr int s16_hv_off(int k) { return 8 * k - (k * (k - 1)) / 2; }
+#define S16_TWIST 6    // twist index of the factorisation (largest-residual-free row), as float
+#define S16_INVTR 7    // 1 / trace(M)
+#define S16_Q 8        // 64: Q'[i][j] (i, j = 1..8) at 8 i + (j - 1): row i is slice i of the record
+#define S16_TD 72      // 9 doubles: diagonal of T  (T = Q^T (M / trace M) Q)
+#define S16_TE 90      // 8 doubles: off-diagonal of T
+#define S16_LAM 106    // 1 double: the selected eigenvalue of M / trace M
+#define S16_Z 108      // 9: z = Q^T f, the unit eigenvector of T, oriented like f (largest-magnitude component of f positive)
+#define S16_U3 117     // smallest singular triplet of F = reshape(f): u3 (3 floats)
+#define S16_V3 120     //                                              v3 (3 floats)
+#define S16_S3 123     //                                              s3 >= 0
+                       // floats 124, 125: unused (zero)
+#define S16_MARK 126   // layout mark: tells this layout from the reflector layout, which carried the same tag and a zero here
+#define S16_MARK_VALUE 64.0f  // 64: Q' as 8 x 8
+#define S16_TAG 127    // record tag: the backward poisons its output unless both the tag and the mark are those of this layout
+#define S16_TAG_VALUE 17.0f
+static_assert(S16_Q == 8 && S16_INVTR < S16_Q && S16_TD >= S16_Q + 64 && S16_TD % 2 == 0 && S16_TE == S16_TD + 18 && S16_LAM == S16_TE + 16 &&
+              S16_Z >= S16_LAM + 2 && S16_S3 < S16_MARK && S16_TAG == DFEPE_SAVE_FLOATS - 1,
+              "slices 1..8 of the record hold the rows of Q' only; the fp64 pieces are 8-byte aligned; nothing overlaps");
 
 struct W8Args {
   const float* pts1;
@@ -277,14 +285,32 @@ __device__ __forceinline__ double row_bilinear(const double* a, const double* b,
 
 __device__ __forceinline__ double pivot_guard(double q) { return (fabs(q) < 1e-30) ? -1e-30 : q; }
 
+// y = diag(1, Q') x for a vector x the whole row shares: lane i (1..8) forms component i from its own row of Q' -- two independent
+// accumulators, no exchange -- and nine broadcasts make the result uniform again.  (The forward's f = Q z, the backward's f = Q z
+// and u = Q y; the lanes outside 1..8 compute something nobody reads.)
+__device__ __forceinline__ void basis_apply(const double* Qr, const double* x, double* y) {
+  const double e = fma(Qr[7], x[7], fma(Qr[5], x[5], fma(Qr[3], x[3], Qr[1] * x[1])));
+  const double o = fma(Qr[8], x[8], fma(Qr[6], x[6], fma(Qr[4], x[4], Qr[2] * x[2])));
+  const double s = e + o;
+  y[0] = x[0];
+  static_for<1, 9>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    y[c] = rg_bcast<c>(s);
+  });
+}
+
 // ---- the eigen phase shared by nothing but this kernel, kept separate for readability -----------------------------
 // In: Ar = row `l` of M / trace(M) (lanes 0..8; zeros elsewhere), kth = number of eigenvalues to pass over.
 // Out (uniform over the row): f[9] unit eigenvector (unoriented), z[9] its tridiagonal-space image, twist, lam, td, te;
-//      per lane: hv[k] = component l of reflector k; hb[k] uniform.
+//      per lane: Qr[1..8] = row l of Q' (lanes 1..8), where diag(1, Q') = H_0 H_1 ... H_6 is the product of the seven reflectors
+//      H_k = I - beta_k v_k v_k^T (H_k acts on components k+1..8).  Q' is accumulated while tridiagonalising -- Q' <- Q' H_k costs
+//      the same two chains as one reflector application, every lane on its own row -- and then f = diag(1, Q') z is plain FMAs on
+//      the lane's row plus nine broadcasts: the back-transform through the reflectors (14 dependent chains) is gone, here and,
+//      twice, in the backward.
 // FUSED_SWEEPS (the lean build): the twisted factorisation keeps ~18 instead of 36 doubles live, same operations in the same order.
 template <bool FUSED_SWEEPS = false>
 __device__ __forceinline__ void eig9_select(double* Ar, const int l, const int kth, double* f, double* z, int& twist,
-                                            double& lam, double* td, double* te, double* hv, double* hb) {
+                                            double& lam, double* td, double* te, double* Qr) {
   // Householder tridiagonalisation, lower form: step k annihilates column k below the sub-diagonal
   static_for<0, 7>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
@@ -299,15 +325,27 @@ __device__ __forceinline__ void eig9_select(double* Ar, const int l, const int k
     const double vtv = fma(vk1, vk1, sig);
     const double beta = ok ? 2.0 * rcp_nr<2, false>(vtv) : 0.0;
     te[k] = ok ? alpha : x1;
-    hb[k] = beta;
-    const double v = ok ? ((l == k + 1) ? vk1 : ((l > k + 1) ? xk : 0.0)) : 0.0;
-    hv[k] = v;
+    const double v = ok ? ((l == k + 1) ? vk1 : ((l > k + 1) ? xk : 0.0)) : 0.0;  // zero outside lanes k+1..8
     // p = beta A v (rows > k), K = beta/2 v^T p, w = p - K v, A -= v w^T + w v^T
     double p = rg_dot_bcast<k + 1>(v, Ar);  // one fused broadcast-FMA per term (rowgroup.h)
+    // Q' <- Q' H_k = Q' - beta (Q' v) v^T, independent of the chain that updates A.  Step 0 starts from the identity, where
+    // (Q' v)_l = v_l exactly; a step with nothing to annihilate has beta = 0, v = 0 and leaves Q' as it is.
+    // Placement (phase stamps at 4096 pairs, profiles/basis_matrix.md): the dot beside A's dot and the update behind A's, as here,
+    // 3883 cycles for this phase; both at the end of the step 3899; deferred under the next step's square root 4001; all seven
+    // behind the loop 3965 -- the lone wavefront is bound by what it issues, there is no idle slot to move them into.
+    double pq;
+    if constexpr (k == 0) {
+#pragma unroll
+      for (int j = 0; j < 9; ++j) Qr[j] = (j == l) ? 1.0 : 0.0;
+      pq = v;
+    } else {
+      pq = rg_dot_bcast<k + 1>(v, Qr);
+    }
     p = (l > k) ? p * beta : 0.0;
     const double K = 0.5 * beta * rg_sum_to8<k + 1>(v * p);
     const double w = fma(-K, v, p);
     rg_axpy2_bcast<k + 1>(Ar, w, -v, v, -w);
+    rg_axpy_bcast<k + 1>(Qr, v, -beta * pq);
   });
   td[7] = rg_bcast<7>(Ar[7]);
   td[8] = rg_bcast<8>(Ar[8]);
@@ -430,15 +468,10 @@ __device__ __forceinline__ void eig9_select(double* Ar, const int l, const int k
   for (int k = 0; k < 9; ++k) zn = fma(z[k], z[k], zn);
   zn = rsqrt_nr<2, false>(zn);  // >= 1: z[twist] = 1
 #pragma unroll
-  for (int k = 0; k < 9; ++k) { z[k] *= zn; f[k] = z[k]; }
+  for (int k = 0; k < 9; ++k) z[k] *= zn;
 
   DFEPE_MARK("P4d_backtransform");
-  // f = H_0 H_1 ... H_6 z, every lane keeps the whole vector (the reflector components come in by broadcast)
-  static_for<0, 7>([&](auto kc) {
-    constexpr int k = 6 - decltype(kc)::value;
-    const double s = -hb[k] * rg_dot_bcast<k + 1>(hv[k], f);
-    rg_axpy_bcast<k + 1>(f, hv[k], s);
-  });
+  basis_apply(Qr, z, f);
 }
 
 // ---- cooperative variant: ROWS = 16 rows (one 256-thread workgroup) share ONE pair ------------------------------------
@@ -781,20 +814,25 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
   // (DeepFNet.py:232-233): for N >= 9 the smallest eigenvalue of X^T X; for N < 9 the reduced SVD has only N columns,
   // so the reference takes the smallest of the N non-null directions: 9 - N eigenvalues are passed over.
   const int kth = (N >= 9) ? 0 : 9 - N;
-  double z[9], td[9], te[8], hv[7], hb[7], lam;
+  double z[9], td[9], te[8], Qr[9], lam;
   int twist;
-  eig9_select<LEAN>(Ar, l, kth, f, z, twist, lam, td, te, hv, hb);
-  // The `save` record in the LEAN build: everything but the reflector components is uniform over the row, and lane s of
-  // {0, 1, 2, 8..15} assembles floats 8 s .. 8 s + 7 of it with one select per float (see the stores at the end of the solver phases).
-  // Here the pieces are folded into the lane's slice AS SOON AS THEY ARE FINAL -- the tridiagonal, the eigenvalue and the reflector
-  // scales right now, z and f after the orientation, the singular triplet after the rank-2 step -- so that 9 + 8 + 1 + 7 doubles stop
+  eig9_select<LEAN>(Ar, l, kth, f, z, twist, lam, td, te, Qr);
+  // the lane's row of Q' as the record takes it (lanes 1..8): final here, so the fp64 row dies before the rank-2 step in both builds
+  const bool qlane = l >= 1 && l <= 8;
+  float qf[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) qf[c] = qlane ? (float)Qr[c + 1] : 0.0f;
+  // The `save` record in the LEAN build: everything but the rows of Q' is uniform over the row, and lane s of {0, 9..15}
+  // assembles floats 8 s .. 8 s + 7 of it with one select per float (see the stores at the end of the solver phases).
+  // Here the pieces are folded into the lane's slice AS SOON AS THEY ARE FINAL -- the tridiagonal and the eigenvalue right now,
+  // z after the orientation, the singular triplet after the rank-2 step -- so that 9 + 8 + 1 doubles stop
   // being live across the rank-2 step (part of what takes that build from 289 to <= 256 registers).  The resident build keeps
   // round 4's code, which assembles the whole record at the end: at one wavefront per SIMD the early selects measured 3-4 % slower
   // (12.5 -> 13.0 us at 4096 pairs, scripts/ab_fit_sizes.py).
   const bool saving = LEAN && A.save != nullptr;
   float slice[LEAN ? 8 : 1];
 #pragma unroll
-  for (int c = 0; c < (LEAN ? 8 : 1); ++c) slice[c] = 0.0f;
+  for (int c = 0; c < (LEAN ? 8 : 1); ++c) slice[c] = LEAN ? qf[c] : 0.0f;
   auto put = [&](const int idx, const float v) {  // idx is a literal after unrolling: slice[] is indexed at compile time
     if constexpr (LEAN) slice[idx & 7] = ((idx >> 3) == l) ? v : slice[idx & 7];
   };
@@ -804,7 +842,6 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
     put(idx, h[0]);
     put(idx + 1, h[1]);
   };
-  float hvf[7];
   if constexpr (LEAN) {
     if (saving) {
 #pragma unroll
@@ -813,9 +850,8 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
       for (int c = 0; c < 8; ++c) put2(S16_TE + 2 * c, te[c]);
       put2(S16_LAM, lam);
       put(S16_TWIST, (float)twist);
-#pragma unroll
-      for (int c = 0; c < 7; ++c) { put(S16_HB + c, (float)hb[c]); hvf[c] = (float)hv[c]; }
       put(S16_INVTR, (float)inv_tr);
+      put(S16_MARK, S16_MARK_VALUE);
       put(S16_TAG, S16_TAG_VALUE);
     }
   }
@@ -836,7 +872,7 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
   if constexpr (LEAN) {
     if (saving) {
 #pragma unroll
-      for (int c = 0; c < 9; ++c) { put(S16_F + c, (float)f[c]); put(S16_Z + c, (float)(sgn * z[c])); }
+      for (int c = 0; c < 9; ++c) put(S16_Z + c, (float)(sgn * z[c]));
     }
   }
 
@@ -891,16 +927,15 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
   if (saving) {
     float* sv = static_cast<float*>(__builtin_assume_aligned(A.save, 16)) + (size_t)pair * DFEPE_SAVE_FLOATS;
     // Under load a global store INSTRUCTION costs this lone wavefront 50-70 cycles whatever its width or the number of lanes behind
-    // it (scripts/ubench/lat2.hip), a select 5: so the uniform part (floats 0..23 and 64..127 of the record) leaves in TWO
-    // instructions -- each lane's slice as two 16-byte pieces -- instead of the 26 stores a lane per piece needed (rounds 2-3).
-    // Floats 24..63 hold only reflector components, which live in their lanes.
+    // it (scripts/ubench/lat2.hip), a select 5: so the whole record leaves in TWO instructions -- each of the 16 lanes' slices as
+    // two 16-byte pieces, lanes 1..8 their row of Q', the others the uniform pieces -- instead of the 26 stores a lane per piece
+    // needed (rounds 2-3) or the two plus seven per-reflector stores of the reflector layout.
     put(S16_T1 + 0, (float)s1); put(S16_T1 + 1, (float)c1x); put(S16_T1 + 2, (float)c1y);
     put(S16_T2 + 0, (float)s2); put(S16_T2 + 1, (float)c2x); put(S16_T2 + 2, (float)c2y);
 #pragma unroll
     for (int c = 0; c < 3; ++c) { put(S16_U3 + c, (float)u3[c]); put(S16_V3 + c, (float)v3[c]); }
     put(S16_S3, (float)s3);
-    static_assert(S16_Z + 9 <= 24 && S16_HV >= 24 && S16_HV + 35 <= 64 && S16_HB >= 64 && S16_TD >= 64, "slices 3..7 of the record hold reflector components only");
-    if (l < 3 || l >= 8) {
+    {
       float4* dst = reinterpret_cast<float4*>(sv + 8 * l);
       float4 q0, q1;
       q0.x = slice[0]; q0.y = slice[1]; q0.z = slice[2]; q0.w = slice[3];
@@ -908,21 +943,18 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
       dst[0] = q0;
       dst[1] = q1;
     }
-#pragma unroll
-    for (int k = 0; k < 7; ++k)  // lanes that hold no component of reflector k write a scratch slot: no branch per reflector
-      sv[(l > k && l < 9) ? S16_HV + s16_hv_off(k) + (l - k - 1) : 24] = hvf[k];
   }
   } else {
   if (A.save != nullptr && storer) {
     float* sv = static_cast<float*>(__builtin_assume_aligned(A.save, 16)) + (size_t)pair * DFEPE_SAVE_FLOATS;
-    // Everything but the reflector components is uniform over the row.  Under load a global store INSTRUCTION costs this lone
+    // Everything but the rows of Q' is uniform over the row.  Under load a global store INSTRUCTION costs this lone
     // wavefront 50-70 cycles whatever its width or the number of lanes behind it (scripts/ubench/lat2.hip), a select 5: so the
-    // uniform part (floats 0..23 and 64..127 of the record) leaves in TWO instructions -- lane s of {0, 1, 2, 8..15} assembles
-    // floats 8 s .. 8 s + 7 with one select per float (~95 v_cndmask) and stores them as two 16-byte pieces -- instead of the
-    // 26 stores a lane per piece needed (rounds 2-3).  Floats 24..63 hold only reflector components, which live in their lanes.
+    // whole record leaves in TWO instructions -- lanes 1..8 hold their row of Q', lane s of {0, 9..15} assembles
+    // floats 8 s .. 8 s + 7 with one select per float (~62 v_cndmask) -- every lane stores its slice as two 16-byte pieces --
+    // instead of the 26 stores a lane per piece needed (rounds 2-3) or the two plus seven per-reflector stores of the reflector layout.
     float slice[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) slice[c] = 0.0f;
+    for (int c = 0; c < 8; ++c) slice[c] = qf[c];
     auto put = [&](const int idx, const float v) {  // idx is a literal after unrolling: slice[] is indexed at compile time
       slice[idx & 7] = ((idx >> 3) == l) ? v : slice[idx & 7];
     };
@@ -935,7 +967,7 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
     put(S16_T1 + 0, (float)s1); put(S16_T1 + 1, (float)c1x); put(S16_T1 + 2, (float)c1y);
     put(S16_T2 + 0, (float)s2); put(S16_T2 + 1, (float)c2x); put(S16_T2 + 2, (float)c2y);
 #pragma unroll
-    for (int c = 0; c < 9; ++c) { put(S16_F + c, (float)f[c]); put(S16_Z + c, (float)(sgn * z[c])); }
+    for (int c = 0; c < 9; ++c) put(S16_Z + c, (float)(sgn * z[c]));
 #pragma unroll
     for (int c = 0; c < 9; ++c) put2(S16_TD + 2 * c, td[c]);
 #pragma unroll
@@ -945,12 +977,10 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
     for (int c = 0; c < 3; ++c) { put(S16_U3 + c, (float)u3[c]); put(S16_V3 + c, (float)v3[c]); }
     put(S16_S3, (float)s3);
     put(S16_TWIST, (float)twist);
-#pragma unroll
-    for (int c = 0; c < 7; ++c) put(S16_HB + c, (float)hb[c]);
     put(S16_INVTR, (float)inv_tr);
+    put(S16_MARK, S16_MARK_VALUE);
     put(S16_TAG, S16_TAG_VALUE);
-    static_assert(S16_Z + 9 <= 24 && S16_HV >= 24 && S16_HV + 35 <= 64 && S16_HB >= 64 && S16_TD >= 64, "slices 3..7 of the record hold reflector components only");
-    if (l < 3 || l >= 8) {
+    {
       float4* dst = reinterpret_cast<float4*>(sv + 8 * l);
       float4 q0, q1;
       q0.x = slice[0]; q0.y = slice[1]; q0.z = slice[2]; q0.w = slice[3];
@@ -958,9 +988,6 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
       dst[0] = q0;
       dst[1] = q1;
     }
-#pragma unroll
-    for (int k = 0; k < 7; ++k)  // lanes that hold no component of reflector k write a scratch slot: no branch per reflector
-      sv[(l > k && l < 9) ? S16_HV + s16_hv_off(k) + (l - k - 1) : 24] = (float)hv[k];
   }
   }
   if constexpr (ROWS > 2) {

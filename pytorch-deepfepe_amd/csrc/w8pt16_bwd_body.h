@@ -141,32 +141,35 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
   // ---- the forward's record (row-uniform loads) and the pair's correspondences -------------------------------
   const double s1 = sv[S16_T1], c1x = sv[S16_T1 + 1], c1y = sv[S16_T1 + 2];
   const double s2 = sv[S16_T2], c2x = sv[S16_T2 + 1], c2y = sv[S16_T2 + 2];
-  double f[9], z[9], td[9], te[8], hb[7], hv[7];
+  double f[9], z[9], td[9], te[8], Qr[9];
 #pragma unroll
-  for (int c = 0; c < 9; ++c) { f[c] = sv[S16_F + c]; z[c] = sv[S16_Z + c]; td[c] = reinterpret_cast<const double*>(sv + S16_TD)[c]; }
+  for (int c = 0; c < 9; ++c) { z[c] = sv[S16_Z + c]; td[c] = reinterpret_cast<const double*>(sv + S16_TD)[c]; }
 #pragma unroll
   for (int c = 0; c < 8; ++c) te[c] = reinterpret_cast<const double*>(sv + S16_TE)[c];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    hb[k] = sv[S16_HB + k];
-    // unconditional load from a clamped slot, then a select: a load under `?:` compiles to branch + load + wait, seven
-    // dependent memory round trips in a row
-    const bool own = l > k && l < 9;
-    const float hvk = sv[own ? S16_HV + s16_hv_off(k) + (l - k - 1) : S16_SCRATCH];
-    hv[k] = own ? (double)hvk : 0.0;
+  {
+    // the lane's row of Q' (lanes 1..8; the others read row 1 and use nothing of it): slice l of the record, two 16-byte loads
+    // from an index-clamped address, unconditional like every other load of this block
+    const int lq = (l >= 1 && l <= 8) ? l : 1;
+    const float4* qp = reinterpret_cast<const float4*>(static_cast<const float*>(__builtin_assume_aligned(A.save, 16)) +
+                                                       (size_t)pair * DFEPE_SAVE_FLOATS + 8 * lq);
+    const float4 q0 = qp[0], q1 = qp[1];
+    Qr[0] = 0.0;
+    Qr[1] = q0.x; Qr[2] = q0.y; Qr[3] = q0.z; Qr[4] = q0.w;
+    Qr[5] = q1.x; Qr[6] = q1.y; Qr[7] = q1.z; Qr[8] = q1.w;
   }
   const double lam = reinterpret_cast<const double*>(sv + S16_LAM)[0];
   // d loss / d F_out and its scale: loaded here (null-safe addresses) with everything else, not where they are first used
   float gF_in[9];
   {
-    const float* gp = (A.g_F != nullptr) ? A.g_F + (size_t)pair * 9 : sv + S16_F;
+    const float* gp = (A.g_F != nullptr) ? A.g_F + (size_t)pair * 9 : sv + S16_Z;
 #pragma unroll
     for (int c = 0; c < 9; ++c) gF_in[c] = gp[c];
   }
   const float gs_in = ((A.g_scale != nullptr) ? A.g_scale : sv + S16_TAG)[l & 0];  // a vector load: the scalar cache would miss
   const int twist = (int)sv[S16_TWIST];
   const double inv_tr = sv[S16_INVTR];
-  const bool good = sv[S16_TAG] == S16_TAG_VALUE;  // a record of another layout (an older library) would be misread: poison instead
+  // a record of another layout would be misread: poison instead.  The tag alone cannot tell the reflector layout from this one.
+  const bool good = sv[S16_TAG] == S16_TAG_VALUE && sv[S16_MARK] == S16_MARK_VALUE;
 
   // same unconditional loads and the same drop rule as the forward (w8pt16_fwd_pair, phase 0); IT = 0: any N, re-read per pass
   constexpr int ITR = (IT > 0) ? IT : 1;
@@ -332,6 +335,7 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
 #pragma unroll
   for (int c = 0; c < 3; ++c) { u3[c] = sv[S16_U3 + c]; v3[c] = sv[S16_V3 + c]; }
   const double s3 = sv[S16_S3];
+  basis_apply(Qr, z, f);  // f = Q z: the record holds z and Q, not f (every row of a cooperative workgroup, for pass B)
   if (ROWS == 1 || rowid == 0) {
   // ---- uniform part (one row per pair) ------------------------------------------------------------------------
   // g_F' = T2 g_out T1^T with T = [[s,0,-s cx],[0,s,-s cy],[0,0,1]] written out
@@ -390,26 +394,22 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
       for (int c = 0; c < 3; ++c) gf[3 * r + c] = G[3 * r + c] - pv[r] * v3[c] - u3[r] * qv[c] + gx[3 * r + c];
   }
   DFEPE_MARK("B4_eigadj");
-  // eigenvector adjoint: u = -(1/trace) H (T - lam I)^+ H^T g_f.  H^T = H_6 ... H_0 (each H_k symmetric).
+  // eigenvector adjoint: u = -(1/trace) Q (T - lam I)^+ Q^T g_f with Q = diag(1, Q').
   {
-    double gt[9], y[9];
-#pragma unroll
-    for (int c = 0; c < 9; ++c) gt[c] = gf[c];
-    static_for<0, 7>([&](auto kc) {
-      constexpr int k = decltype(kc)::value;
-      const double s = -hb[k] * rg_dot_bcast<k + 1>(hv[k], gt);  // fused broadcast-FMA chains (rowgroup.h)
-      rg_axpy_bcast<k + 1>(gt, hv[k], s);
+    double gt[9], y[9], qy[9];
+    // Q^T g_f: component c is sum_i Q'[i][c] g_i, lane i contributing its Q'[i][c] by broadcast -- eight chains that do not depend
+    // on one another (fused broadcast-FMA, rowgroup.h), uniform over the row as tri_pinv_apply wants it
+    gt[0] = gf[0];
+    static_for<1, 9>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      gt[c] = rg_dot_bcast<1>(Qr[c], gf);
     });
   DFEPE_MARK("B5_tripinv");
     tri_pinv_apply(td, te, lam, z, twist, gt, y);
-    static_for<0, 7>([&](auto kc) {
-      constexpr int k = 6 - decltype(kc)::value;
-      const double s = -hb[k] * rg_dot_bcast<k + 1>(hv[k], y);
-      rg_axpy_bcast<k + 1>(y, hv[k], s);
-    });
+    basis_apply(Qr, y, qy);
     const double sc = good ? -inv_tr : (double)NAN;
 #pragma unroll
-    for (int c = 0; c < 9; ++c) u[c] = sc * y[c];
+    for (int c = 0; c < 9; ++c) u[c] = sc * qy[c];
   }
   if constexpr (ROWS > 1) {
     if (l < 9) co->u[l] = u[l];

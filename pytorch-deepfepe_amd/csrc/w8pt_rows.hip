@@ -66,9 +66,9 @@ w8pt_rows_kernel(const float* __restrict__ rows, int B, int N, unsigned variant,
   for (int j = 0; j < 9; ++j) Ar[j] *= inv_tr;
   // torch.svd(XX, some=True)[2][:, -1]: for N < 9 the smallest of the N non-null directions (as in the fit kernels)
   const int kth = (N >= 9) ? 0 : 9 - N;
-  double f[9], z[9], td[9], te[8], hv[7], hb[7], lam;
+  double f[9], z[9], td[9], te[8], Qr[9], lam;  // Qr: the lane's row of the tridiagonalising basis (no record is written here)
   int twist;
-  eig9_select(Ar, l, kth, f, z, twist, lam, td, te, hv, hb);
+  eig9_select(Ar, l, kth, f, z, twist, lam, td, te, Qr);
   double fn2 = 0.0, big = f[0];
 #pragma unroll
   for (int c = 0; c < 9; ++c) fn2 = fma(f[c], f[c], fn2);

@@ -19,10 +19,14 @@ Fo = torch.empty(B, 9, device="cuda"); res = torch.empty(B, N, device="cuda"); e
 sv = torch.empty(B, 128, device="cuda"); wo = torch.empty(B, N, device="cuda")
 gF = torch.randn(B, 9, device="cuda"); gl = torch.empty(B, N, device="cuda")
 st = torch.cuda.current_stream().cuda_stream
-assert libs[0].dfepe_w8pt_fwd(m.data_ptr(), None, lg.data_ptr(), B, N, 1, 3, 1241.0, 376.0, 0.5, Fo.data_ptr(), res.data_ptr(), epi.data_ptr(),
-                               sv.data_ptr(), wo.data_ptr(), st) == 0
+# every build reads the record its own forward wrote: the record's layout belongs to the build
+svs = {}
+for L in libs:
+    svs[id(L)] = torch.empty_like(sv)
+    assert L.dfepe_w8pt_fwd(m.data_ptr(), None, lg.data_ptr(), B, N, 1, 3, 1241.0, 376.0, 0.5, Fo.data_ptr(), res.data_ptr(), epi.data_ptr(),
+                            svs[id(L)].data_ptr(), wo.data_ptr(), st) == 0
 def launch(L):
-    rc = L.dfepe_w8pt_bwd(m.data_ptr(), None, wo.data_ptr(), B, N, 1, 3, 1241.0, 376.0, 0.5, sv.data_ptr(), Fo.data_ptr(), gF.data_ptr(), None, None,
+    rc = L.dfepe_w8pt_bwd(m.data_ptr(), None, wo.data_ptr(), B, N, 1, 3, 1241.0, 376.0, 0.5, svs[id(L)].data_ptr(), Fo.data_ptr(), gF.data_ptr(), None, None,
                           None, None, gl.data_ptr(), None, None, None, st)  # g_weights_extra, g_scale, g_weights, g_pts1, g_pts2, pending head
     assert rc == 0
 def t(L, n=50):

@@ -102,7 +102,7 @@ int main(int argc, char** argv) {
   std::vector<unsigned long long> clk((size_t)waves * 16);
   hipMemcpy(clk.data(), dclk, clk.size() * 8, hipMemcpyDeviceToHost);
   const char* names[8] = {"B0 loads (save record, g_F, correspondences)", "B1 pass A (upstream per-correspondence terms: compiled out)", "B2 uniform: T2 g T1^T",
-                          "B3 rank-2 adjoint", "B4 eigenvector adjoint: reflect g_f", "B5 (T - lam I)^+ and back", "B6 pass B: g_w, softmax adjoint, stores", "end"};
+                          "B3 rank-2 adjoint", "B4 eigenvector adjoint: Q^T g_f", "B5 (T - lam I)^+ and back", "B6 pass B: g_w, softmax adjoint, stores", "end"};
   double sum[8] = {0}, mx[8] = {0};
   for (int w = 0; w < waves; ++w) {
     const unsigned long long* c = &clk[(size_t)w * 16];
