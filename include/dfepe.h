@@ -640,7 +640,7 @@ int dfepe_knn_match(const float *desc1, const float *desc2, int B, int N1, int N
  * batched.  Replaces: cv2.findFundamentalMat(x1, x2, cv2.RANSAC, 0.1) in utils_opencv.recover_camera_opencv
  * (deepFEPE/dsac_tools/utils_opencv.py:157), the validation baseline of val_rt (train_good_utils.py:615-633).
  *   matches [B,N,4] fp32 pixels (x1, y1, x2, y2), 16-byte aligned; 15 <= N <= 4096 (N < 15: DFEPE_ERR_UNSUPPORTED -- OpenCV
- *     switches to LMedS there, which is not built; N > 4096: the pair does not fit in LDS); B <= 65535 (else UNSUPPORTED)
+ *     switches to LMedS there: dfepe_lmeds_fundamental; N > 4096: the pair does not fit in LDS); B <= 65535 (else UNSUPPORTED)
  *   threshold t (pixels, >= 0), confidence p in [0, 1], max_iters >= 1, seed: see the algorithm below
  *   workspace  dfepe_ransac_workspace_bytes(B, N, max_iters) bytes of device memory, 16-byte aligned, overwritten
  *   F_out [B,9] fp32 (F22 = 1; zeros when the pair has no model); inlier_mask [B,N] uint8; n_inliers [B] int32 (0: no model);
@@ -725,6 +725,62 @@ int dfepe_ransac_essential(const float *matches, const float *K, int B, int N, d
                            int max_iters, unsigned long long seed, void *workspace, float *E_out,
                            unsigned char *inlier_mask, int *n_inliers, int *iters_run, int *best_hyp,
                            int *hyp_counts, double *hyp_E, float *masked_matches, void *stream);
+
+/*
+ * Least-median-of-squares fundamental and essential matrix of every pair: OpenCV 3.4's LMeDSPointSetRegistrator::run, batched.
+ * Replaces: what cv2.findFundamentalMat(x1, x2, cv2.RANSAC, 0.1) (deepFEPE/dsac_tools/utils_opencv.py:157) runs on a pair with
+ * fewer than 15 correspondences -- OpenCV does not run RANSAC there but LMedS, and no threshold is used -- and
+ * cv2.findEssentialMat(.., method=LMEDS), which is what recover_camera_opencv(five_point=True, RANSAC=False) (:137-151) means in
+ * OpenCV.  The pose that follows is dfepe_cheirality_ex on masked_matches and dfepe_ransac_in_front, as for the RANSAC entries.
+ *   matches [B,N,4] fp32 pixels (x1, y1, x2, y2), 16-byte aligned; K [B,9] fp32 as for dfepe_ransac_essential.
+ *     Fundamental: 8 <= N <= 4096 (N = 7 is OpenCV's direct 7-point path, not built); essential: 6 <= N <= 4096; outside:
+ *     DFEPE_ERR_UNSUPPORTED; B <= 65535 (else UNSUPPORTED); confidence p in [0, 1], max_iters >= 1 (else INVALID_ARG); a NULL
+ *     required pointer is INVALID_ARG; B == 0 returns 0 before any launch.  m = 7 (fundamental) or 5 (essential) below.
+ *   dfepe_lmeds_num_iters(m, p, max_iters): niters of step 1 (negative: INVALID_ARG); it sizes hyp_medians.
+ *   workspace  dfepe_lmeds_workspace_bytes(B, m, p, max_iters) bytes of device memory, 16-byte aligned, overwritten
+ *   F_out / E_out [B,9] fp32 (the winning root as the RANSAC entries scale it; zeros when the pair has no model); inlier_mask
+ *   [B,N] uint8; n_inliers [B] int32 (0: no model); iters_run [B] int32 (iterations the loop went through); best_hyp [B,2] int32
+ *   (winning iteration and root, -1 -1 without a model; may be NULL); min_median [B] fp64 (DBL_MAX when no median was finite;
+ *   may be NULL); sigma [B] fp64 (0 when no median was finite; may be NULL); hyp_medians [B,niters,3] resp. [B,niters,10] fp64 or
+ *   NULL: the median table (median of root r of iteration k, an fp32 value or +inf; -1 = no such root, -2 = the iteration drew no
+ *   sample; with NULL the table lives in the workspace); masked_matches [B,N,4] or NULL: the matches with every non-inlier row
+ *   set to quiet NaN.
+ * The algorithm (sequential definition; the device evaluates all niters iterations in parallel and applies the rule of step 5 to
+ * the medians, with the same result):
+ *   1 niters = RANSACUpdateNumIters(p, 0.45, m, max_iters) (the rule of dfepe_ransac_fundamental resp. dfepe_ransac_essential),
+ *     fixed for the whole run: 300 for p = 0.99, m = 7.  There is no adaptive update.  niters = 0 (p = 0): no model.
+ *   2 Iteration k samples and solves exactly as the RANSAC entry of the same m does: the same stream and key_k, for m = 7 the
+ *     same collinearity redraw (no sample at k = 0: no model; at k > 0: the loop ends there), the same 7-point resp. five-point
+ *     solve (for m = 5 on the normalised coordinates of dfepe_ransac_essential step 0): up to 3 resp. 10 models.
+ *   3 The error of every correspondence under every model, evaluated in fp64 and rounded to fp32: for F max(d1^2, d2^2) in px^2
+ *     with the divisions by the line norms (d2: distance of x2 to F x1, d1: of x1 to F^T x2); for E the Sampson error
+ *     (q2^T E q1)^2 / ((E q1)_0^2 + (E q1)_1^2 + (E^T q2)_0^2 + (E^T q2)_1^2) in normalised coordinates.  A zero denominator or a
+ *     non-finite value counts as +inf.
+ *   4 Median: the fp32 errors sorted ascending (by their bit patterns as integers: valid for non-negative floats); odd N:
+ *     sorted[N/2]; even N: (sorted[N/2 - 1] + sorted[N/2]) * 0.5 with the sum in fp32.
+ *   5 Select: through k = 0, 1, ... and the roots in order, a model becomes the best when its median is strictly below
+ *     minMedian, which starts at DBL_MAX: an infinite median never wins.
+ *   6 sigma = max(2.5 * 1.4826 * (1 + 5 / (N - m)) * sqrt(minMedian), 0.001); a correspondence is an inlier when its fp32 error
+ *     is <= (float)(sigma^2).  Fewer than m inliers: no model (zeros, best_hyp = -1 -1, n_inliers = 0; min_median and sigma keep
+ *     their values).  There is no refit.
+ * What differs from OpenCV: the random stream (as for the RANSAC entries), and the errors are the fp32 rounding of an fp64
+ * evaluation, not a float evaluation, so near-ties between two medians can fall the other way.  OpenCV also replaces a confidence
+ * outside (0, 1) by 0.99 before it starts; here 0 and 1 are taken as given.
+ * The median is a selection, not a sort: one wavefront per model holds the N errors in ceil(N / 64) registers per lane and finds
+ * the rank-N/2 pattern from the most significant bit down (31 rounds of a per-lane count and a wavefront sum).  No atomics: two
+ * calls on the same input are bit-identical, and a pair's result does not depend on the batch around it.
+ * dfepe_version() stays 154 with this addition: the number is pinned by existing tests, and nothing that existed changes.
+ */
+int dfepe_lmeds_num_iters(int model_points, double confidence, int max_iters);
+size_t dfepe_lmeds_workspace_bytes(int B, int model_points, double confidence, int max_iters);
+int dfepe_lmeds_fundamental(const float *matches, int B, int N, double confidence, int max_iters, unsigned long long seed,
+                            void *workspace, float *F_out, unsigned char *inlier_mask, int *n_inliers, int *iters_run,
+                            int *best_hyp, double *min_median, double *sigma, double *hyp_medians, float *masked_matches,
+                            void *stream);
+int dfepe_lmeds_essential(const float *matches, const float *K, int B, int N, double confidence, int max_iters,
+                          unsigned long long seed, void *workspace, float *E_out, unsigned char *inlier_mask, int *n_inliers,
+                          int *iters_run, int *best_hyp, double *min_median, double *sigma, double *hyp_medians,
+                          float *masked_matches, void *stream);
 
 /*
  * Optimal correction of correspondences onto a given epipolar geometry (Hartley & Sturm), batched: for every pair (p, q) the pair

@@ -25,12 +25,14 @@ W8PT16_MAX_N = 128
 TAIL_MAX_LAYERS = 16  # dfepe_loss_tail: layers per launch (kTailMaxLayers, csrc/loss_tail_body.h)
 EPI_HOMOGENEOUS = 8
 CHEIR_FP64_ONLY = 1
-RANSAC_MIN_N = 15  # dfepe_ransac_fundamental: below, OpenCV switches to LMedS (not built)
+RANSAC_MIN_N = 15  # dfepe_ransac_fundamental: below, OpenCV switches to LMedS (dfepe_lmeds_fundamental)
 POSE_CHAIN_THREADS = 256  # dfepe_pose_chain: lanes per sequence (kChainThreads, csrc/odometry.hip)
 POSE_CHAIN_CHUNK = 8  # ... and consecutive poses per lane and tile (kChainChunk): a tile is 2048 poses
 SNIPPET_MAX_L = 64  # dfepe_snippet_errors: longest snippet (kSnipMaxL)
 TRAJ_MODES = ("none", "scale", "scale_7dof", "7dof", "6dof")  # dfepe_trajectory_align: mode = index (DFEPE_TRAJ_*, traj::Mode)
 KITTI_DIST_LDS = 4096  # dfepe_kitti_odometry_errors: frames whose path length stays in LDS (kDistLds, csrc/trajectory.hip)
+LMEDS_MIN_N = 8  # dfepe_lmeds_fundamental: N = 7 is OpenCV's direct 7-point path (not built)
+LMEDS5_MIN_N = 6  # dfepe_lmeds_essential
 RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked models of the one sample (not built)
 
 _P = c_void_p
@@ -112,6 +114,10 @@ _SIGNATURES = {
     "dfepe_ransac_in_front": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
     "dfepe_ransac5_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_ransac_essential": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfepe_lmeds_num_iters": (c_int, [c_int, c_double, c_int]),
+    "dfepe_lmeds_workspace_bytes": (c_size_t, [c_int, c_int, c_double, c_int]),
+    "dfepe_lmeds_fundamental": (c_int, [_P, c_int, c_int, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfepe_lmeds_essential": (c_int, [_P, _P, c_int, c_int, c_double, c_int, c_ulonglong, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_correct_matches": (c_int, [_P, _P, c_long, _P, _P, c_int, c_int, _P, _P, _P]),
     "dfepe_pose_chain": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, _P]),
     "dfepe_snippet_errors": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),

@@ -452,7 +452,10 @@ def val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=True, depth_
     Rt_cam_opencv, winner_opencv, F_opencv, E_opencv, inlier_mask_opencv.
     ``baseline="five_point"``: the OpenCV five-point baseline instead (val_rt's five_point=True leg, :615-633:
     ops.ransac_essential_pose at the 0.01 px val_rt passes), under the keys err_R_deg_opencv5p, err_t_deg_opencv5p,
-    Rt_cam_opencv5p, winner_opencv5p, E_opencv5p, F_opencv5p (= K^-T E K^-1), inlier_mask_opencv5p."""
+    Rt_cam_opencv5p, winner_opencv5p, E_opencv5p, F_opencv5p (= K^-T E K^-1), inlier_mask_opencv5p.
+    ``baseline="lmeds"`` / ``baseline="lmeds_five_point"``: the same two legs with least median of squares in place of RANSAC
+    (ops.lmeds_pose, ops.lmeds_essential_pose: what OpenCV runs on a pair with fewer than 15 correspondences, resp. with
+    method=LMEDS; no threshold), under the same keys ending in _lmeds resp. _lmeds5p."""
     E = E_ests.float()
     if not E.is_cuda:
         raise _lib.DfepeError("val_rt_batch: tensors must live on the GPU")
@@ -467,7 +470,25 @@ def val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=True, depth_
     err_R = torch.where(bad, torch.full_like(err_R, 180.0), err_R)
     err_t = torch.where(bad, torch.full_like(err_t, 90.0), err_t)
     out = {"err_R_deg": err_R, "err_t_deg": err_t, "Rt_cam": Rt, "winner": win, "counts": cnt}
-    if baseline == "five_point":
+    if baseline in ("lmeds", "lmeds_five_point"):
+        from .utils_opencv import recover_pose_camera
+
+        K = Ks.to(dev).float()
+        five = baseline == "lmeds_five_point"
+        tag = "_lmeds5p" if five else "_lmeds"
+        b = ops.lmeds_essential_pose(matches_xy.to(dev), K, depth_thres=depth_thres) if five else \
+            ops.lmeds_pose(matches_xy.to(dev), K, depth_thres=depth_thres, K_pose=recover_pose_camera(K))
+        Rb = b["Rt_cam"]
+        eR = ops.rot_angle_deg(Rb[:, :, :3].contiguous(), gt[:, :3, :3].contiguous())
+        et = ops.vector_angle_deg(Rb[:, :, 3].contiguous(), gt[:, :3, 3].contiguous())
+        bad = b["winner"] < 0
+        Kinv = torch.linalg.inv(K)
+        out.update({"err_R_deg" + tag: torch.where(bad, torch.full_like(eR, 180.0), eR),
+                    "err_t_deg" + tag: torch.where(bad, torch.full_like(et, 90.0), et),
+                    "Rt_cam" + tag: Rb, "winner" + tag: b["winner"], "E" + tag: b["E"],
+                    "F" + tag: Kinv.transpose(1, 2) @ b["E"] @ Kinv if five else b["F"],
+                    "inlier_mask" + tag: b["mask"]})
+    elif baseline == "five_point":
         from .utils_opencv import FIVE_POINT_THRESHOLD
 
         K = Ks.to(dev).float()
@@ -505,7 +526,8 @@ def validation_summary(Ks, matches_xy, E_ests, F_ests, F_gts, delta_Rtijs_4_4, p
     Returns (summary dict of python floats for the 'ours' tag, per-pair dict of device tensors).
     ``baseline``: val_rt_batch's OpenCV 8-point baseline too, its epipolar distances (per-pair key epi_dists_opencv) and its
     summary (key "opencv_8p" of the summary dict, the reference's tag for it).  ``baseline="five_point"``: the five-point
-    baseline instead: per-pair key epi_dists_opencv5p, summary key "opencv_5p"."""
+    baseline instead: per-pair key epi_dists_opencv5p, summary key "opencv_5p".  ``baseline="lmeds"`` / ``"lmeds_five_point"``:
+    the least-median baselines: per-pair keys epi_dists_lmeds / epi_dists_lmeds5p, summary keys "lmeds_8p" / "lmeds_5p"."""
     from . import utils_F
 
     pairs = val_rt_batch(Ks, matches_xy, E_ests, delta_Rtijs_4_4, project_E=project_E, depth_thres=depth_thres, baseline=baseline)
@@ -514,7 +536,13 @@ def validation_summary(Ks, matches_xy, E_ests, F_ests, F_gts, delta_Rtijs_4_4, p
     d_gt = 2.0 * utils_F._epi_distance(F_gts, X, Y)[0]
     pairs.update({"epi_dists": d_est, "epi_dists_gt": d_gt})
     summary = ops.metrics_summary(d_est, d_gt, pairs["err_R_deg"], pairs["err_t_deg"])
-    if baseline == "five_point":
+    if baseline in ("lmeds", "lmeds_five_point"):
+        tag = "_lmeds5p" if baseline == "lmeds_five_point" else "_lmeds"
+        d_ocv = 2.0 * utils_F._epi_distance(pairs["F" + tag].contiguous(), X, Y)[0]
+        pairs["epi_dists" + tag] = d_ocv
+        summary["lmeds_5p" if baseline == "lmeds_five_point" else "lmeds_8p"] = ops.metrics_summary(d_ocv, d_gt, pairs["err_R_deg" + tag],
+                                                                                                  pairs["err_t_deg" + tag])
+    elif baseline == "five_point":
         d_ocv = 2.0 * utils_F._epi_distance(pairs["F_opencv5p"].contiguous(), X, Y)[0]
         pairs["epi_dists_opencv5p"] = d_ocv
         summary["opencv_5p"] = ops.metrics_summary(d_ocv, d_gt, pairs["err_R_deg_opencv5p"], pairs["err_t_deg_opencv5p"])

@@ -3,8 +3,10 @@ utils_opencv.py:129-208), backed by the batched RANSAC estimator of libdfepe_hip
 
 What differs from OpenCV: the random stream (include/dfepe.h, dfepe_ransac_fundamental), so results agree with cv2's in
 distribution, not bit for bit.  The five-point baseline (cv2.findEssentialMat, Nister's solver) is recover_camera_five_point,
-backed by ops.ransac_essential_pose; recover_camera_opencv(five_point=True) itself still raises.  Not built: LMedS (OpenCV's
-choice for fewer than 15 correspondences of the 8-point branch).
+backed by ops.ransac_essential_pose; recover_camera_opencv(five_point=True) itself still raises.  LMedS, OpenCV's choice for
+fewer than 15 correspondences of the 8-point branch, is ops.lmeds_pose: recover_camera_opencv takes it for 8 <= N < 15 as OpenCV
+does, and recover_camera_lmeds runs it (or its five-point form, cv2.findEssentialMat(method=LMEDS)) on any pair.  Not built: the
+direct 7-point solve OpenCV runs on exactly 7 correspondences.
 
 KNN_match (utils_opencv.py:39-90) is backed by ops.knn_match: the exact k = 2 search of cv2.BFMatcher(NORM_L2).knnMatch with
 Lowe's ratio test.  What differs from OpenCV: ``if_BF=False`` selects FLANN's randomised kd-trees (5 trees, 50 checks) in the
@@ -15,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .._lib import LMEDS_MIN_N, RANSAC_MIN_N
 
 BASELINE_THRESHOLD = 0.1  # the reference's 8-point branch passes 0.1 to findFundamentalMat whatever `threshold` says (:157)
 FIVE_POINT_THRESHOLD = 0.01  # what val_rt passes to the five-point branch, which uses it (train_good_utils.py:622)
@@ -56,7 +59,10 @@ def recover_camera_opencv(K, x1, x2, delta_Rtij_inv, five_point=False, threshold
     Kt = torch.as_tensor(K, dtype=torch.float32, device=dev).reshape(1, 3, 3)
     K_pose = torch.eye(3, device=dev).reshape(1, 3, 3) if if_normalized else recover_pose_camera(Kt)
     if E_given is None:
-        out = ops.ransac_pose(m, Kt, threshold=BASELINE_THRESHOLD, K_pose=K_pose)
+        if LMEDS_MIN_N <= m.shape[1] < RANSAC_MIN_N:  # cv2.findFundamentalMat(.., cv2.RANSAC, ..) runs LMedS there; no threshold
+            out = ops.lmeds_pose(m, Kt, K_pose=K_pose)
+        else:
+            out = ops.ransac_pose(m, Kt, threshold=BASELINE_THRESHOLD, K_pose=K_pose)
         E, F = out["E"], out["F"]
         Rt_cam, win, in_front = out["Rt_cam"], out["winner"], out["in_front"]
         F_np = F[0].cpu().double().numpy()
@@ -105,6 +111,39 @@ def recover_camera_five_point(K, x1, x2, delta_Rtij_inv, threshold=0.1, show_res
         print("Recovered by OpenCV %s (camera): The rotation error (degree) %.4f, and translation error (degree) %.4f"
               % ("5 point" + method_app, err[0], err[1]))
     return M, err, mask2, out["E"][0].cpu().double().numpy()
+
+
+def recover_camera_lmeds(K, x1, x2, delta_Rtij_inv, five_point=False, show_result=True, if_normalized=False, method_app=""):
+    """The pose of one pair by least median of squares, with the reference's return for either branch.
+    five_point=False: what cv2.findFundamentalMat(x1, x2, cv2.RANSAC, 0.1) computes below 15 correspondences (utils_opencv.py:157),
+    here for any 8 <= N <= 4096, by ops.lmeds_pose; returns (np.hstack((R, t)) [3,4], (error_R, error_t) degrees, mask2 [N] bool,
+    (E, F)) like recover_camera_opencv.  five_point=True: cv2.findEssentialMat(.., method=cv2.LMEDS) -- what RANSAC=False means in
+    OpenCV's five-point branch (:137-151) -- by ops.lmeds_essential_pose; returns (M, errors, mask2, E) like
+    recover_camera_five_point.  LMedS takes no threshold.  ``if_normalized``: focal 1 and principal point (0, 0) for the pose step
+    (and, with five_point, for the estimate).  A pair without a pose gets the identity, (180, 90) and an all-False mask."""
+    dev = torch.device("cuda")
+    m = torch.as_tensor(np.hstack((np.asarray(x1), np.asarray(x2))), dtype=torch.float32, device=dev).unsqueeze(0).contiguous()
+    Kt = torch.as_tensor(np.asarray(K, dtype=np.float64), dtype=torch.float32, device=dev).reshape(1, 3, 3)
+    eye = torch.eye(3, device=dev).reshape(1, 3, 3)
+    if five_point:
+        out = ops.lmeds_essential_pose(m, eye if if_normalized else Kt)
+    else:
+        out = ops.lmeds_pose(m, Kt, K_pose=eye if if_normalized else recover_pose_camera(Kt))
+    Rt_cam = out["Rt_cam"]
+    mask2 = out["in_front"][0].cpu().numpy() > 0
+    if int(out["winner"][0].item()) < 0:
+        M = np.hstack((np.eye(3), np.zeros((3, 1))))
+        err = FAILED
+    else:
+        err = _pose_errors(Rt_cam[0], delta_Rtij_inv)
+        R = Rt_cam[0, :, :3].t()
+        t = -(R @ Rt_cam[0, :, 3].reshape(3, 1))
+        M = torch.cat((R, t), 1).cpu().double().numpy()
+    if show_result:
+        print("Recovered by OpenCV %s (camera): The rotation error (degree) %.4f, and translation error (degree) %.4f"
+              % (("5 point" if five_point else "8 point") + " LMedS" + method_app, err[0], err[1]))
+    E = out["E"][0].cpu().double().numpy()
+    return M, err, mask2, (E if five_point else (E, out["F"][0].cpu().double().numpy()))
 
 
 def KNN_match(des1, des2, x1_all, x2_all, kp1, kp2, img1_rgb, img2_rgb, visualize=False, if_BF=False, if_ratio_test=True):

@@ -22,7 +22,7 @@ namespace {
 constexpr int kChunk = 64;                        // iterations per workgroup of the count launch
 constexpr int kHyps = kChunk * rs::kMaxRoots;     // hypotheses per workgroup
 constexpr int kMaxN = 4096;                       // correspondences staged in LDS (16 B each)
-constexpr int kMinN = 15;                         // below: OpenCV switches to LMedS (not built)
+constexpr int kMinN = 15;                         // below: OpenCV switches to LMedS (lmeds.hip)
 constexpr int kMaxPairs = 65535;                  // pairs go on the grid's y dimension
 
 __global__ void __launch_bounds__(256) ransac_count_kernel(const float4* __restrict__ matches, int N, int max_iters, double t2,

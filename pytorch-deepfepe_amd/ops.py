@@ -940,13 +940,13 @@ def ransac_fundamental(matches: Tensor, threshold: float = 0.1, confidence: floa
     baseline, utils_opencv.py:157; include/dfepe.h spells out the sampler, the 7-point solve, the error and the stopping rule).
     Returns dict(F [B,3,3] (F22 = 1; zeros without a model), mask [B,N] uint8, n_inliers [B], iters_run [B], best_hyp [B,2]
     (iteration, root; -1 without a model), hyp_counts [B,max_iters,3] | None (-1: no root, -2: no sample), masked [B,N,4] | None
-    (non-inlier rows NaN)).  No host synchronisation.  15 <= N <= 4096: below 15 OpenCV runs LMedS, which is not built."""
+    (non-inlier rows NaN)).  No host synchronisation.  15 <= N <= 4096: below 15 OpenCV runs LMedS, which is lmeds_fundamental."""
     m = _prep(matches, "matches")
     _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
     B, N = m.shape[0], m.shape[1]
     if N < _lib.RANSAC_MIN_N:
         raise _lib.DfepeError(f"ransac_fundamental: {N} correspondences per pair; the RANSAC estimator needs at least "
-                              f"{_lib.RANSAC_MIN_N} (OpenCV switches to LMedS below that, which is not built)")
+                              f"{_lib.RANSAC_MIN_N} (OpenCV switches to LMedS below that, which is not built into this entry: see lmeds_fundamental)")
     L = _lib.lib()
     dev = m.device
     ws = torch.empty(max(1, (int(L.dfepe_ransac_workspace_bytes(B, N, int(max_iters))) + 15) // 16), 2, dtype=torch.float64, device=dev)
@@ -1052,6 +1052,101 @@ def ransac_essential_pose(matches: Tensor, K: Tensor, threshold: float = 1.0, co
     Kp[:, 0, 0] = Kp[:, 1, 1] = K[:, 0, 0]
     Kp[:, 0, 2], Kp[:, 1, 2], Kp[:, 2, 2] = K[:, 0, 2], K[:, 1, 2], 1.0
     out = ransac_essential(matches, Kp, threshold, confidence, max_iters, seed, want_masked=True)
+    Rt, win, cnt = cheirality(out["E"], Kp, out["masked"], depth_thres)
+    out.update({"Rt_cam": Rt, "winner": win, "counts": cnt, "in_front": ransac_in_front(out["E"], Kp, out["masked"], win, depth_thres)})
+    return out
+
+
+def _lmeds(name: str, m: Tensor, K: Optional[Tensor], model_points: int, confidence: float, max_iters: int, seed: int,
+           want_hyp_medians: bool, want_masked: bool):
+    """The common body of lmeds_fundamental (K None, model_points 7) and lmeds_essential (model_points 5)."""
+    B, N = m.shape[0], m.shape[1]
+    L = _lib.lib()
+    dev = m.device
+    niters = int(L.dfepe_lmeds_num_iters(model_points, float(confidence), int(max_iters)))
+    if niters < 0:
+        _lib.check(niters, "dfepe_lmeds_num_iters")
+    roots = 3 if model_points == 7 else 10
+    ws = torch.empty(max(1, (int(L.dfepe_lmeds_workspace_bytes(B, model_points, float(confidence), int(max_iters))) + 15) // 16), 2,
+                     dtype=torch.float64, device=dev)
+    out = {
+        name: torch.empty(B, 3, 3, device=dev),
+        "mask": torch.empty(B, N, device=dev, dtype=torch.uint8),
+        "n_inliers": torch.empty(B, device=dev, dtype=torch.int32),
+        "iters_run": torch.empty(B, device=dev, dtype=torch.int32),
+        "best_hyp": torch.empty(B, 2, device=dev, dtype=torch.int32),
+        "min_median": torch.empty(B, device=dev, dtype=torch.float64),
+        "sigma": torch.empty(B, device=dev, dtype=torch.float64),
+        "hyp_medians": torch.empty(B, niters, roots, device=dev, dtype=torch.float64) if want_hyp_medians else None,
+        "masked": torch.empty(B, N, 4, device=dev) if want_masked else None,
+    }
+    tail = (B, N, float(confidence), int(max_iters), int(seed) & ((1 << 64) - 1), _ptr(ws), _ptr(out[name]), _ptr(out["mask"]),
+            _ptr(out["n_inliers"]), _ptr(out["iters_run"]), _ptr(out["best_hyp"]), _ptr(out["min_median"]), _ptr(out["sigma"]),
+            _ptr(out["hyp_medians"]), _ptr(out["masked"]), _stream())
+    with _on(dev):
+        rc = L.dfepe_lmeds_fundamental(_ptr(m), *tail) if K is None else L.dfepe_lmeds_essential(_ptr(m), _ptr(K), *tail)
+    _lib.check(rc, "dfepe_lmeds_fundamental" if K is None else "dfepe_lmeds_essential")
+    return out
+
+
+def lmeds_fundamental(matches: Tensor, confidence: float = 0.99, max_iters: int = 1000, seed: int = 0, want_hyp_medians: bool = False,
+                      want_masked: bool = False):
+    """matches [B,N,4] pixels -> least-median-of-squares F of every pair: OpenCV 3.4's LMedS, which cv2.findFundamentalMat(..,
+    cv2.RANSAC, ..) runs instead of RANSAC below 15 correspondences (utils_opencv.py:157; include/dfepe.h spells out the six
+    steps).  No threshold: the inlier bound comes from the winning median.
+    Returns dict(F [B,3,3] (F22 = 1; zeros without a model), mask [B,N] uint8, n_inliers [B], iters_run [B], best_hyp [B,2]
+    (iteration, root; -1 without a model), min_median [B] float64, sigma [B] float64, hyp_medians [B,niters,3] float64 | None
+    (-1: no root, -2: no sample; niters = 300 for the default confidence), masked [B,N,4] | None (non-inlier rows NaN)).
+    No host synchronisation.  8 <= N <= 4096."""
+    m = _prep(matches, "matches")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    if m.shape[1] < _lib.LMEDS_MIN_N:
+        raise _lib.DfepeError(f"lmeds_fundamental: {m.shape[1]} correspondences per pair; the LMedS estimator needs at least "
+                              f"{_lib.LMEDS_MIN_N} (with 7 OpenCV solves the one sample directly, which is not built)")
+    return _lmeds("F", m, None, 7, confidence, max_iters, seed, want_hyp_medians, want_masked)
+
+
+def lmeds_pose(matches: Tensor, K: Tensor, confidence: float = 0.99, max_iters: int = 1000, seed: int = 0, depth_thres: float = 50.0,
+               K_pose: Optional[Tensor] = None):
+    """ransac_pose with lmeds_fundamental in place of ransac_fundamental: what utils_opencv.recover_camera_opencv computes for a
+    pair with fewer than 15 correspondences (utils_opencv.py:157-177).  Returns the lmeds_fundamental dict with E [B,3,3], Rt_cam
+    [B,3,4], winner [B], counts [B,4] and in_front [B,N] uint8 added."""
+    K = _prep(K, "K")
+    out = lmeds_fundamental(matches, confidence, max_iters, seed, want_masked=True)
+    B = out["F"].shape[0]
+    _shape(K, "K (one intrinsic matrix per pair)", B, 3, 3)
+    Kp = K if K_pose is None else _prep(K_pose, "K_pose")
+    E = project_essential(congruence(out["F"], K))
+    Rt, win, cnt = cheirality(E, Kp, out["masked"], depth_thres)
+    out.update({"E": E, "Rt_cam": Rt, "winner": win, "counts": cnt, "in_front": ransac_in_front(E, Kp, out["masked"], win, depth_thres)})
+    return out
+
+
+def lmeds_essential(matches: Tensor, K: Tensor, confidence: float = 0.999, max_iters: int = 1000, seed: int = 0,
+                    want_hyp_medians: bool = False, want_masked: bool = False):
+    """matches [B,N,4] pixels, K [B,3,3] -> least-median-of-squares E of every pair by five-point models: OpenCV 3.4's
+    findEssentialMat(method=LMEDS) (include/dfepe.h, dfepe_lmeds_essential).  Returns the dict of lmeds_fundamental with E [B,3,3]
+    (unit Frobenius norm; zeros without a model) in place of F and hyp_medians [B,niters,10].  No host synchronisation.
+    6 <= N <= 4096."""
+    m, K = _prep(matches, "matches"), _prep(K, "K")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    _shape(K, "K (one intrinsic matrix per pair)", m.shape[0], 3, 3)
+    if m.shape[1] < _lib.LMEDS5_MIN_N:
+        raise _lib.DfepeError(f"lmeds_essential: {m.shape[1]} correspondences per pair; the five-point LMedS estimator needs at least "
+                              f"{_lib.LMEDS5_MIN_N}")
+    return _lmeds("E", m, K, 5, confidence, max_iters, seed, want_hyp_medians, want_masked)
+
+
+def lmeds_essential_pose(matches: Tensor, K: Tensor, confidence: float = 0.999, max_iters: int = 1000, seed: int = 0,
+                         depth_thres: float = 50.0):
+    """ransac_essential_pose with lmeds_essential in place of ransac_essential (the same camera recover_pose_camera(K) for the
+    estimate and for the pose).  Returns the lmeds_essential dict with Rt_cam [B,3,4], winner [B], counts [B,4] and in_front [B,N]
+    uint8 added."""
+    K = _prep(K, "K")
+    Kp = torch.zeros_like(K)  # compat.utils_opencv.recover_pose_camera: focal K00, principal point (K02, K12)
+    Kp[:, 0, 0] = Kp[:, 1, 1] = K[:, 0, 0]
+    Kp[:, 0, 2], Kp[:, 1, 2], Kp[:, 2, 2] = K[:, 0, 2], K[:, 1, 2], 1.0
+    out = lmeds_essential(matches, Kp, confidence, max_iters, seed, want_masked=True)
     Rt, win, cnt = cheirality(out["E"], Kp, out["masked"], depth_thres)
     out.update({"Rt_cam": Rt, "winner": win, "counts": cnt, "in_front": ransac_in_front(out["E"], Kp, out["masked"], win, depth_thres)})
     return out
