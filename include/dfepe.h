@@ -315,6 +315,13 @@ int dfepe_w8pt_pose_fwd(const float *matches, const float *weights, int B, int N
  *     uint64 counts[8]  = #est<0.1, #est<1, (TP, FP, FN) at 0.1, (TP, FP, FN) at 1.0
  *     uint64 hist[2][12] bin counts for err_q, err_t (bins [th_k, th_k+1), the last closed; values outside [0,180] dropped)
  *     float  max[2], float mids[2][2] = the two middle order statistics of err_q, err_t (median = their mean)
+ *   comparisons: est, gt against 0.1f and 1.0f in float32; the histogram in float64 against the float64 thresholds, as
+ *     np.histogram does (a float32 error next to a rounded threshold lands where numpy puts it)
+ *   max: the largest entry that is > 0, NaN if any entry is NaN, +0.0 otherwise (-0.0 and negative entries never win: np.amax of
+ *     a vector with one entry >= 0); mids: NaN if any entry is NaN
+ *   median: the caller forms 0.5 * (mids[0] + mids[1]) in float64 and does NOT round it back to float32 -- np.median of the errors
+ *     widened to float64; np.median of the float32 vector would round the mean
+ *   B = 0 or n_epi = 0: nothing is launched for that half, its part of the record stays zero
  * Raw counts, not ratios: the host derives the ratios after ONE device-to-host copy per validation epoch.
  */
 size_t dfepe_metrics_summary_bytes(void);
@@ -358,6 +365,13 @@ int dfepe_epi_residual_bwd(const float *pts1, const float *pts2, const float *F,
  *                                                                                   utils_F._F_to_E's K^T F K, utils_F.py:456)
  *   kind 6  camera rotation of a scene motion  in0 = delta [n,16]       out [n,9] = inv(delta)[:3,:3]
  *                                                                                  (get_Rt_loss, train_good_utils.py:134,170)
+ * Kind 2 is the reference's formula acos(clip(v1.v2 / ((|v1| + 1e-10)(|v2| + 1e-10) + 1e-10))) as it stands: at |v| ~ 1 the three
+ * 1e-10 terms leave the cosine of parallel vectors at 1 - 3e-10, so equal vectors report about 1.4e-3 degrees (opposite ones
+ * 180 - 1.4e-3) and every near-parallel direction error carries that floor; 0 and 180 come out exactly only where the terms are
+ * absorbed (|v| >~ 1e6).  A zero vector reports 90.
+ * Every kind computes in float64 from the float32 inputs and rounds once.  A NaN in an item's inputs makes that item's outputs NaN
+ * and touches no other item (kinds 3 and 4: any NaN or infinity in E makes all of the item's outputs NaN).  Kinds 3 and 4 return
+ * orthonormal factors for every finite E, a rank-1 or zero matrix included, where the projection itself is not defined.
  */
 int dfepe_geo_misc(int kind, const float *in0, const float *in1, int n, float *out, void *stream);
 

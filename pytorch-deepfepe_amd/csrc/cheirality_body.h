@@ -12,9 +12,10 @@ namespace {
 
 // the four-fold ambiguity of utils_F._get_M2s (utils_F.py:478-498): R1 = U W V^T, R2 = U W^T V^T (both negated when
 // det < 0), t = u3 / |u3|
+template <int NEWTON_STEPS = 12>
 __device__ inline void decompose_E(const double* E, double* R1, double* R2, double* t) {
   double U[9], S[3], V[9];
-  svd3_closed(E, U, S, V);
+  svd3_closed<NEWTON_STEPS>(E, U, S, V);
   double UW[9], UWt[9];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {

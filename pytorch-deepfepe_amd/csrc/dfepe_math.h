@@ -216,7 +216,7 @@ __device__ __forceinline__ void sym3_null_vector(double c00, double c01, double 
 }
 
 // F row-major, assumed O(1) in magnitude (the solver passes a unit-Frobenius F).  Returns s3 >= 0, unit u3, v3.
-template <bool ROBUST = false>
+template <bool ROBUST = false, int NEWTON_STEPS = 12>
 __device__ __forceinline__ void smallest_singular_triplet3(const double* F, double* u3, double* v3, double& s3) {
   // B = F^T F
   const double b00 = F[0] * F[0] + F[3] * F[3] + F[6] * F[6], b01 = F[0] * F[1] + F[3] * F[4] + F[6] * F[7];
@@ -235,11 +235,14 @@ __device__ __forceinline__ void smallest_singular_triplet3(const double* F, doub
   };
   // Four steps without a branch: the relative error goes (s3/s2)^2 -> its square -> ..., so a generic matrix is converged after
   // three; the loop behind them (entered only while the fourth step still moved x) covers s3 ~ s2.  A data-dependent exit after
-  // every step costs more in exec-mask bookkeeping than the arithmetic it skips.
+  // every step costs more in exec-mask bookkeeping than the arithmetic it skips.  Next to a double root Newton only halves its
+  // distance per step: NEWTON_STEPS = 12 stop 6e-5 short of s3^2 at (s2 - s3) / s1 = 1e-6, and the null vectors of a shift that is no
+  // eigenvalue are arbitrary.  The stand-alone pose helpers (geom.hip, kinds 3 and 4), which take whatever E they are given, ask for 64
+  // (tests/pose_helper_cases.py: small_gap); the training path keeps 12.
   double dx = 0.0;
 #pragma unroll
   for (int it = 0; it < 4; ++it) { dx = newton(); x += dx; }
-  for (int it = 4; it < 12 && dx > 0.0; ++it) { dx = newton(); x += dx; }
+  for (int it = 4; it < NEWTON_STEPS && dx > 0.0; ++it) { dx = newton(); x += dx; }
   sym3_null_vector<ROBUST>(b00 - x, b01, b02, b11 - x, b12, b22 - x, v3);
   // D = F F^T
   const double d00 = F[0] * F[0] + F[1] * F[1] + F[2] * F[2], d01 = F[0] * F[3] + F[1] * F[4] + F[2] * F[5];
@@ -274,6 +277,7 @@ __device__ __forceinline__ void orthonormal_complement3(const double* n, double*
 // above, then the 2x2 problem in the orthogonal complements of u3 / v3, whose one Jacobi rotation is exact.  ~450 straight-line
 // instructions against ~170 per sweep of the one-sided Jacobi it replaced (4-6 sweeps).  Repeated s1 = s2 (essential matrices) is fine:
 // any orthonormal pair of the plane is a valid answer, and U, V are produced consistently (u_i = F v_i / s_i).
+template <int NEWTON_STEPS = 12>
 __device__ inline void svd3_closed(const double* Fin, double* U, double* S, double* V) {
   // exact power-of-two prescale to max|F| in [0.5, 1): the vectors do not depend on the scale, S is scaled back exactly, and the
   // closed forms / Newton seeds see O(1) entries whatever the scale of the input (an essential matrix times 1e-6 used to leave
@@ -287,7 +291,7 @@ __device__ inline void svd3_closed(const double* Fin, double* U, double* S, doub
 #pragma unroll
   for (int i = 0; i < 9; ++i) F[i] = ldexp(Fin[i], -ex);
   double u3[3], v3[3], s3;
-  smallest_singular_triplet3<true>(F, u3, v3, s3);
+  smallest_singular_triplet3<true, NEWTON_STEPS>(F, u3, v3, s3);
   double a1[3], a2[3], b1[3], b2[3];
   orthonormal_complement3(v3, a1, a2);
   orthonormal_complement3(u3, b1, b2);

@@ -144,6 +144,15 @@ __device__ inline void quat_of(const double* R, double* q) {
   for (int k = 0; k < 4; ++k) q[k] = sc * v[k];
 }
 
+// svd3_closed answers a matrix holding a NaN or an infinity with finite orthonormal factors (each of its selects takes the "no" side of
+// a comparison with NaN): kinds 3 and 4 hand such a row back as NaN, as np.linalg.svd would, so that a diverged E stays visible
+constexpr int kGeoNewton = 64;  // Newton steps of the closed-form SVD's cubic for kinds 3 and 4 (dfepe_math.h: near-double s2 ~ s3)
+__device__ inline bool finite9(const double* E) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) ok = ok && (fabs(E[k]) <= 1.7976931348623157e308);  // false for a NaN and for an infinity
+  return ok;
+}
 
 __global__ void __launch_bounds__(256)
 geo_misc_kernel(int kind, const float* __restrict__ in0, const float* __restrict__ in1, int n, float* __restrict__ out) {
@@ -172,18 +181,20 @@ geo_misc_kernel(int kind, const float* __restrict__ in0, const float* __restrict
       dot += a * b; n1 += a * a; n2 += b * b;
     }
     const double den = (sqrt(n1) + 1e-10) * (sqrt(n2) + 1e-10) + 1e-10;
-    out[i] = (float)(acos(fmin(fmax(dot / den, -1.0), 1.0)) * rad2deg);
+    const double cs = dot / den;  // clipped as np.clip does: a NaN stays a NaN (fmin / fmax would hand back the bound: 180 degrees)
+    out[i] = (float)(acos(cs < -1.0 ? -1.0 : (cs > 1.0 ? 1.0 : cs)) * rad2deg);
   } else if (kind == 3) {
     double E[9], U[9], S[3], V[9], Ed[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) E[k] = (double)in0[i * 9 + k];
-    svd3_closed(E, U, S, V);
+    svd3_closed<kGeoNewton>(E, U, S, V);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
       for (int c = 0; c < 3; ++c) Ed[3 * r + c] = U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1];
+    const bool ok = finite9(E);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) out[i * 9 + k] = (float)Ed[k];
+    for (int k = 0; k < 9; ++k) out[i * 9 + k] = ok ? (float)Ed[k] : __builtin_nanf("");
   } else if (kind == 6) {
     // camera-motion rotation of a scene motion: inv(delta)[:3,:3] for a general 4x4 (cofactors of the full matrix, so the
     // last row need not be (0,0,0,1)); np.linalg.inv(delta_Rtij)[:3,:3] of get_Rt_loss, train_good_utils.py:134,170
@@ -221,11 +232,12 @@ geo_misc_kernel(int kind, const float* __restrict__ in0, const float* __restrict
     double E[9], R1[9], R2[9], t[3];
 #pragma unroll
     for (int k = 0; k < 9; ++k) E[k] = (double)in0[i * 9 + k];
-    decompose_E(E, R1, R2, t);
+    decompose_E<kGeoNewton>(E, R1, R2, t);
+    const bool ok = finite9(E);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) { out[i * 21 + k] = (float)R1[k]; out[i * 21 + 9 + k] = (float)R2[k]; }
+    for (int k = 0; k < 9; ++k) { out[i * 21 + k] = ok ? (float)R1[k] : __builtin_nanf(""); out[i * 21 + 9 + k] = ok ? (float)R2[k] : __builtin_nanf(""); }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out[i * 21 + 18 + k] = (float)t[k];
+    for (int k = 0; k < 3; ++k) out[i * 21 + 18 + k] = ok ? (float)t[k] : __builtin_nanf("");
   }
 }
 

@@ -65,9 +65,10 @@ __global__ void __launch_bounds__(256) err_stats_kernel(const float* __restrict_
     const unsigned cnt = wave_count(bin == k);
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&hist[which * (kNumThs - 1) + k], (unsigned long long)cnt);
   }
-  // non-negative floats order like their bit patterns, and the canonical NaN pattern sits above +inf: one NaN error makes the
-  // maximum NaN, as np.amax does (a diverged run must stay visible, train_good_utils.py:811-816)
-  if (live && (x >= 0.0f || x != x)) atomicMax(&maxbits[which], (x != x) ? 0x7FC00000u : __float_as_uint(x));
+  // positive floats order like their bit patterns, and the canonical NaN pattern sits above +inf: one NaN error makes the
+  // maximum NaN, as np.amax does (a diverged run must stay visible, train_good_utils.py:811-816).  -0.0f is kept out (x > 0, not
+  // x >= 0): its pattern 0x80000000 is above every positive float, +inf and the NaN; a vector of zeros of either sign reports 0.0
+  if (live && (x > 0.0f || x != x)) atomicMax(&maxbits[which], (x != x) ? 0x7FC00000u : __float_as_uint(x));
   if (live) {
     int less = 0, equal = 0, nans = 0;
     for (int j = 0; j < B; ++j) {

@@ -1353,8 +1353,11 @@ METRIC_THS = (0.0, 0.01, 0.03, 0.05, 0.1, 0.3, 0.5, 1.0, 2.0, 5.0, 10.0, 90.0, 1
 def metrics_summary(epi_est: Tensor, epi_gt: Optional[Tensor], err_q: Tensor, err_t: Tensor) -> dict:
     """Device-side reductions of write_metrics_summary (train_good_utils.py:758-856) for one experiment tag: epi_est / epi_gt
     = epipolar distances of every correspondence (any shape, same numel), err_q / err_t [B] pose errors in degrees.
-    Two launches and ONE device-to-host copy of 280 bytes.  Returns python floats: ratio_0.1, ratio_1, F1_0.1, F1_1 (None
-    without epi_gt), median / max of err_q and err_t, and ratio_q / ratio_t = cumulative fractions below METRIC_THS[1:]."""
+    Two launches and ONE device-to-host copy of 288 bytes.  Returns python floats: ratio_0.1, ratio_1, F1_0.1, F1_1 (None
+    without epi_gt), median / max of err_q and err_t, and ratio_q / ratio_t = cumulative fractions below METRIC_THS[1:].
+    The median is np.median of the errors widened to float64: the float64 mean of the two middle float32 order statistics, not
+    rounded back to float32.  The maximum is np.amax for any vector with an entry >= 0 or NaN (NaN wins, -0.0 never does).  Empty
+    inputs give zeros.  tests/metrics_ref.py restates all of it; tests/test_metrics_edges_gpu.py compares exactly."""
     import numpy as np
 
     e = _prep(epi_est.reshape(-1), "epi_est")
