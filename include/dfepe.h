@@ -936,6 +936,49 @@ int dfepe_kitti_odometry_errors(void *stream, const double *est, const double *g
                                 int n_max, int step, int F, double *dist, double *rows, unsigned char *valid, int *count,
                                 double *summary);
 
+/*
+ * Two-view structure: the 3-D points and depths that the pose kernels reduce to one bit each, and the projection back.
+ * Common rules: B < 0 or N < 0 (M < 0), an unknown flag bit, a stride other than 0 (one matrix for all pairs) or the row size
+ * (12 for a 3x4, 9 for K): INVALID_ARG; then B == 0 or N == 0 returns 0 before any launch; then a required pointer that is NULL,
+ * or matches (and Xh, which is written as float4 too) not 16-byte aligned: INVALID_ARG; then B > 65535: UNSUPPORTED.  All of
+ * it is decided on the host before any HIP call.  One launch per call, one lane per correspondence, no host synchronisation, no
+ * allocation, nothing written outside the stated extents; a non-finite row touches only its own outputs.
+ *
+ * dfepe_triangulate: cv2.triangulatePoints for B pairs.
+ *   P1, P2 3x4 fp32 projection matrices (stride 0 or 12); matches [B,N,4] pixels (x1, y1, x2, y2); Xh [B,N,4] fp32.
+ *   Per correspondence Xh is the unit 2-norm null vector (last right singular vector) of the 4x4 matrix
+ *     A = [x1 P1_3 - P1_1; y1 P1_3 - P1_2; x2 P2_3 - P2_1; y2 P2_3 - P2_2]      (P_i: row i; the published DLT),
+ *   computed in fp64 from the fp32 inputs (one-sided Jacobi on A itself, csrc/triangulate_math.h) and rounded once, with the sign
+ *   w = Xh[3] >= 0 (OpenCV leaves the sign to its SVD; every call site divides by w).  Scaling both matrices by the same power of
+ *   two changes no bit.  A non-finite match row, a non-finite matrix or A = 0 give four NaNs for that row only.
+ *   Accuracy (tests/triangulate_ref.py): with s1 >= .. >= s4 the singular values of A and
+ *     eta = max(1e-8, 64 2^-52 s1^2 / (s3^2 - s4^2)),  |Xh - Xh_ref|_inf <= eta + 2^-24 wherever eta is finite.
+ *
+ * dfepe_two_view_structure: the points and depths of a pose's correspondences (DeepFNet.get_depth after cv2.recoverPose).
+ *   Rt [B,3,4] fp32: scene motion (x2 ~ R x1 + t), or with DFEPE_POSE_CAMERA_MOTION camera motion -- what dfepe_cheirality_ex
+ *   writes -- whose inverse R = Rc^T, t = -Rc^T tc (utils_misc._inv_Rt) is formed in fp64.  K [B,3,3] fp32.  Cameras P1 = K [I | 0],
+ *   P2 = K [R | t] in fp64, the triangulation above, then X = Xh[:3] / w in the frame of camera 1, z1 = X[2], z2 = (R X + t)[2],
+ *   all fp64 up to one rounding.  scale [B] or NULL multiplies X, z1 and z2 (the reference's t_scene_scale: a recovered t has unit
+ *   norm).  clamp > 0 clamps z1 and z2, after scaling, to [-clamp, clamp] (torch.clamp(tri_depths * t_scene_scale, -150., 150.),
+ *   DeepFNetSampleLoss.py:614); X is not clamped; NaN stays NaN.  winner [B] int32 or NULL: a pair with winner < 0 has no pose and
+ *   gets NaN rows.  X [B,N,3], z1, z2 [B,N] fp32: each may be NULL, all three NULL is INVALID_ARG.  w = 0 gives what the fp64
+ *   division gives (inf or NaN); it never traps.
+ *
+ * dfepe_reproject: the numeric part of dsac_tools/utils_vis.reproj_and_scatter.
+ *   X [B,M,3] fp32; Rt (stride 0 or 12) and flags as above; K (stride 0 or 9).  u = K (R X + t) in fp64 from the fp32 inputs,
+ *   x [B,M,2] = (u0 / u2, u1 / u2) and z [B,M] = u2 rounded once; inside [B,M] bytes = (x >= 0) & (y >= 0) & (x <= image_w) &
+ *   (y <= image_h) evaluated on the fp32 values written to x (utils_misc.within with xlim = im_shape[1], ylim = im_shape[0]):
+ *   NaN gives 0, and there is no depth test, as in the reference.  z and inside may be NULL.
+ */
+#define DFEPE_POSE_CAMERA_MOTION 1u   /* Rt is camera motion (what dfepe_cheirality_ex writes); scene motion is R = Rc^T, t = -Rc^T tc, as utils_misc._inv_Rt */
+
+int dfepe_triangulate(const float *P1, int p1_stride, const float *P2, int p2_stride, const float *matches, int B, int N, float *Xh,
+                      void *stream);
+int dfepe_two_view_structure(const float *Rt, unsigned flags, const float *K, const float *matches, int B, int N, const int *winner,
+                             const float *scale, float clamp, float *X, float *z1, float *z2, void *stream);
+int dfepe_reproject(const float *X, const float *Rt, int rt_stride, unsigned flags, const float *K, int k_stride, int B, int M,
+                    float image_w, float image_h, float *x, float *z, unsigned char *inside, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ TRAJ_MODES = ("none", "scale", "scale_7dof", "7dof", "6dof")  # dfepe_trajectory
 KITTI_DIST_LDS = 4096  # dfepe_kitti_odometry_errors: frames whose path length stays in LDS (kDistLds, csrc/trajectory.hip)
 LMEDS_MIN_N = 8  # dfepe_lmeds_fundamental: N = 7 is OpenCV's direct 7-point path (not built)
 LMEDS5_MIN_N = 6  # dfepe_lmeds_essential
+POSE_CAMERA_MOTION = 1  # dfepe_two_view_structure / dfepe_reproject: Rt is camera motion (DFEPE_POSE_CAMERA_MOTION)
 RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked models of the one sample (not built)
 
 _P = c_void_p
@@ -123,6 +124,9 @@ _SIGNATURES = {
     "dfepe_snippet_errors": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "dfepe_trajectory_align": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "dfepe_kitti_odometry_errors": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dfepe_triangulate": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, _P, _P]),
+    "dfepe_two_view_structure": (c_int, [_P, c_uint, _P, _P, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P]),
+    "dfepe_reproject": (c_int, [_P, _P, c_int, c_uint, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -143,6 +143,30 @@ class DeepFNet(nn.Module):
     def get_input(self, data_batch, offsets=None, iter=None):
         return self._inputs(data_batch, offsets)[:6]
 
+    def get_depth(self, data_batch, F_out, T1, T2):
+        """Triangulated depth in camera 1 of every correspondence under the pose of F_out, [B,1,N] float on the device
+        (DeepFNet.py:406-427): F_ests = T2^T F_out T1, E = K^T F_ests K, the pose of E by ops.cheirality with the camera the
+        reference hands cv2.recoverPose (as recover_camera_opencv(E_given=...) does), then z1 of ops.two_view_structure with the
+        pair's full K.  A pair without a pose gets NaN.  No host synchronisation.  (forward() does not call it: if_tri_depth
+        still raises in the constructor.)"""
+        Rt_cam, winner, K, matches = self._depth_pose(data_batch, F_out, T1, T2)
+        return ops.two_view_structure(Rt_cam, K, matches, camera_motion=True, winner=winner, want=("z1",))["z1"].unsqueeze(1)
+
+    def _depth_pose(self, data_batch, F_out, T1, T2):
+        """The pose get_depth triangulates under: (Rt_cam [B,3,4], winner [B], K, matches)."""
+        from .utils_opencv import recover_pose_camera
+
+        _require_gpu(F_out, "DeepFNet.get_depth")
+        K, matches = data_batch["Ks"].float(), data_batch["matches_xy_ori"]
+        B = F_out.shape[0]
+        if T1 is T2:  # forward()'s image-size transform: one congruence launch
+            F_ests = ops.congruence(F_out.detach(), T1.detach().expand(B, -1, -1))
+        else:
+            F_ests = T2.detach().permute(0, 2, 1) @ F_out.detach() @ T1.detach()
+        E_ests = ops.congruence(F_ests, K)
+        Rt_cam, winner, _ = ops.cheirality(E_ests, recover_pose_camera(K), matches, 50.0)
+        return Rt_cam, winner, K, matches
+
     def _fit(self, matches, logits, data_batch, want_epi, dst=None):
         """logits [B,1,N] -> (out, residual[, epi], weights_prod [B,1,N]).  The softmax over N is fused into the solver
         kernel unless per-correspondence image weights multiply it afterwards (if_img_w).  ``dst``: rows of the per-layer

@@ -9,7 +9,9 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.train_good_utils           ->   compat.train_good_utils (get_all_loss_DeepF, get_Rt_loss, get_matches_from_SP)
     deepFEPE.dsac_tools.utils_misc      ->   compat.utils_misc      (homogeneous / rigid-transform helpers, crop_or_pad_choice,
                                                                     get_virt_x1x2*: the F-loss's virtual points, no cv2)
-    deepFEPE.dsac_tools.utils_opencv    ->   compat.utils_opencv    (recover_camera_opencv: the 8-point RANSAC baseline, no cv2)
+    deepFEPE.dsac_tools.utils_opencv    ->   compat.utils_opencv    (recover_camera_opencv: the 8-point RANSAC baseline, no cv2;
+                                                                    triangulatePoints in place of cv2.triangulatePoints)
+    deepFEPE.dsac_tools.utils_vis       ->   compat.utils_vis       (reproj_and_scatter without the drawing)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)
     deepFEPE.utils.eval_tools           ->   compat.eval_tools      (Exp_table_processor's odometry methods: get_abs_poses,
@@ -20,5 +22,5 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, dsac, eval_tools, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv  # noqa: F401
+from . import DeepFNet, ErrorEstimators, captured, dsac, eval_tools, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401

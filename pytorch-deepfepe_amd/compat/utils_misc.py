@@ -9,6 +9,13 @@ import torch
 from .. import ops
 
 
+def within(x, y, xlim, ylim):
+    """Which points lie inside [0, xlim] x [0, ylim], borders included (utils_misc.py:12-15); numpy, NaN is outside."""
+    val_inds = (x >= 0) & (y >= 0)
+    val_inds = val_inds & (x <= xlim) & (y <= ylim)
+    return val_inds
+
+
 def identity_Rt(dtype=np.float32):
     """[I | 0] as a 3x4 numpy array (utils_misc.py:17-18)."""
     return np.hstack((np.eye(3, dtype=dtype), np.zeros((3, 1), dtype=dtype)))

@@ -12,7 +12,10 @@ KNN_match (utils_opencv.py:39-90) is backed by ops.knn_match: the exact k = 2 se
 Lowe's ratio test.  What differs from OpenCV: ``if_BF=False`` selects FLANN's randomised kd-trees (5 trees, 50 checks) in the
 reference, an approximate search whose answer is not reproducible; here both values of ``if_BF`` run the exact search, so the
 FLANN branch's occasional misses do not occur.  Near-ties inside the float32 error of the distance (include/dfepe.h,
-dfepe_knn_match) may be ordered differently from OpenCV's own float32 summation."""
+dfepe_knn_match) may be ordered differently from OpenCV's own float32 summation.
+
+triangulatePoints stands in for cv2.triangulatePoints (utils_opencv.py:199 and the other call sites listed in its docstring),
+backed by ops.triangulate."""
 import numpy as np
 import torch
 
@@ -31,6 +34,24 @@ def recover_pose_camera(K):
     Kp[:, 0, 0] = Kp[:, 1, 1] = K[:, 0, 0]
     Kp[:, 0, 2], Kp[:, 1, 2], Kp[:, 2, 2] = K[:, 0, 2], K[:, 1, 2], 1.0
     return Kp
+
+
+def triangulatePoints(projMatr1, projMatr2, projPoints1, projPoints2):
+    """cv2.triangulatePoints with cv2's layout, numpy in and out: projMatr1, projMatr2 [3,4], projPoints1, projPoints2 [2,N]
+    -> [4,N] homogeneous points, from one launch (ops.triangulate).  The values are the float32 output of the kernel (fp64
+    arithmetic, one rounding; include/dfepe.h, dfepe_triangulate): every column has unit 2-norm and w = out[3] >= 0, where OpenCV
+    leaves the sign to its SVD -- every call site of the reference divides by w (utils_F.py:554, :712, DeepFNet.py:421-422,
+    utils_opencv.py:199)."""
+    x1, x2 = np.asarray(projPoints1, dtype=np.float32), np.asarray(projPoints2, dtype=np.float32)
+    if x1.ndim != 2 or x1.shape[0] != 2 or x2.shape != x1.shape:
+        raise ValueError(f"projPoints1 and projPoints2 must both be [2,N], got {x1.shape} and {x2.shape}")
+    if x1.shape[1] == 0:
+        return np.zeros((4, 0), dtype=np.float32)
+    dev = torch.device("cuda")
+    m = torch.as_tensor(np.ascontiguousarray(np.vstack((x1, x2)).T), device=dev).unsqueeze(0)
+    P1 = torch.as_tensor(np.ascontiguousarray(projMatr1, dtype=np.float32), device=dev)
+    P2 = torch.as_tensor(np.ascontiguousarray(projMatr2, dtype=np.float32), device=dev)
+    return np.ascontiguousarray(ops.triangulate(P1, P2, m)[0].cpu().numpy().T)
 
 
 def _pose_errors(Rt_cam, delta_Rtij_inv):
