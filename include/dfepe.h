@@ -979,6 +979,86 @@ int dfepe_two_view_structure(const float *Rt, unsigned flags, const float *K, co
 int dfepe_reproject(const float *X, const float *Rt, int rt_stride, unsigned flags, const float *K, int k_stride, int B, int M,
                     float image_w, float image_h, float *x, float *z, unsigned char *inside, void *stream);
 
+/*
+ * Robust homography of every pair: OpenCV 3.4 findHomography(x1, x2, RANSAC, threshold, maxIters, confidence), batched.
+ * Replaces: cv2.findHomography(m_keypoints, m_warped_keypoints, cv2.RANSAC) in evaluations/descriptor_evaluation.py:93-95
+ * (compute_homography) and in deepFEPE/evaluate_frontend.py:234-236 (getInliers_cv).
+ *   matches [B,N,4] fp32 pixels (x1, y1, x2, y2), 16-byte aligned; 1 <= N <= 4096 (N < 1: INVALID_ARG; N > 4096: UNSUPPORTED, the
+ *     pair does not fit in LDS); B <= 65535 (else UNSUPPORTED); B == 0 returns OK
+ *   n_valid [B] int32 or NULL: pair b uses its first n = clamp(n_valid[b], 0, N) rows (cross-checked matches differ in number from
+ *     pair to pair); rows past n get mask 0; NULL means N for every pair
+ *   threshold t in pixels; t <= 0 means 3 (cv2's rule); NaN: INVALID_ARG.  confidence p in [0, 1], max_iters >= 1 (else INVALID_ARG)
+ *   flags: DFEPE_HOMOGRAPHY_ALL_POINTS is cv2's method = 0: no sampling, the mask is all ones, the model is step 6 over all n
+ *     points, then step 7.  DFEPE_HOMOGRAPHY_NO_REFINE skips step 7, so H_out is the refit.  Any other bit: INVALID_ARG
+ *   workspace  dfepe_homography_workspace_bytes(B, N, max_iters) bytes of device memory, 16-byte aligned, overwritten
+ *   H_out [B,9] fp64 (cv2 returns float64), H[8] = 1, zeros when the pair has no model; H_model [B,9] fp64 or NULL: the winning
+ *     sample's H before the refit (with ALL_POINTS: the result of step 6); inlier_mask [B,N] uint8; n_inliers [B] int32 (0: no
+ *     model); iters_run [B] int32 (iterations consumed; 0 where nothing is sampled); best_iter [B] int32 or NULL (-1 without a
+ *     sampled winner); hyp_counts [B,max_iters] int32 or NULL: the count table (-1 = the sample gave no model, -2 = no sample,
+ *     also every entry of a pair with n <= 4; not written with ALL_POINTS)
+ *   All refusals are made before anything is launched.  No atomics; every cell has one writer; two calls on the same input are
+ *   bit-identical; no host synchronisation, no allocation.
+ * The algorithm (sequential definition; the device evaluates all max_iters iterations in parallel and applies the rule to the
+ * counts, with the same result).  OpenCV is not available where this was written and its results are not pinned by golden
+ * vectors: what follows is the definition, held to the fp64 restatement tests/homography_ref.py; only the random stream is ours.
+ *   0 Pair sizes.  n < 4: no model.  n = 4: one solve (step 2) on the four points, mask all ones, no sampling, no refinement.
+ *     A pair without a model gives H = 0, mask 0 and n_inliers = 0.
+ *   1 Sampling.  The stream of dfepe_ransac_fundamental (same key_k, same Lemire map, independent of the pair), 4 distinct indices.
+ *     A sample is redrawn from the same stream when the non-partial checkSubset fails: the last point is collinear with two
+ *     earlier ones in either image (the test of dfepe_ransac_fundamental), or the orientation test fails -- over the triples
+ *     {0,1,2}, {0,1,3}, {0,2,3}, {1,2,3} the number with det[src_i 1] det[dst_i 1] < 0 (each det of the 3x3 matrix of rows
+ *     (x, y, 1), in fp64 from the fp32 coordinates) must be 0 or 4.  After 1000 attempts the iteration has no sample.
+ *   2 4-point solve (runKernel) in fp64: per image the centroid c and the per-axis sums s = sum |x - c|; any s < FLT_EPSILON: no
+ *     model; scales n / s.  With the normalised source (X, Y) and target (x, y) each point gives the rows
+ *     (X, Y, 1, 0, 0, 0, -xX, -xY, -x) and (0, 0, 0, X, Y, 1, -yX, -yY, -y).  For the minimal sample h is the null vector of the
+ *     8x9 system taken directly: Householder QR of its transpose, the last column of Q (not the eigenvector of L^T L; the
+ *     restatement's second route takes the SVD).  H = T_dst^-1 H0 T_src scaled so that H[8] = 1; H[8] zero or not finite before
+ *     the scaling: no model.
+ *   3 Score: err = ((H00 x + H01 y + H02)/w - x')^2 + ((H10 x + H11 y + H12)/w - y')^2 with w = H20 x + H21 y + 1; inlier iff
+ *     err <= t^2, evaluated in fp64 without divisions: (X - x'w)^2 + (Y - y'w)^2 <= t^2 w^2; w = 0 is never an inlier.
+ *   4 Select: the rule of dfepe_ransac_fundamental with one slot per iteration and 4 model points: a model whose count exceeds
+ *     max(best, 3) becomes the best, niters = RANSACUpdateNumIters(p, (n - count)/n, 4, niters), the loop stops at k >= niters or
+ *     at the first iteration without a sample.
+ *   5 Mask: the winner's inliers by step 3.  It is not recomputed after steps 6 and 7 (OpenCV keeps the RANSAC mask).
+ *   6 Refit, when n > 4 and a model was found: runKernel over all inliers of the winner in its n-point form -- centroids, scales,
+ *     the 9x9 L^T L accumulated in fp64, the eigenvector of its smallest eigenvalue by cyclic Jacobi, de-normalised as in 2.
+ *     When this gives no model the winner's H stays (OpenCV ignores the return value); with ALL_POINTS the pair then has none.
+ *   7 Refinement: Levenberg-Marquardt, at most 10 iterations, on h[0..7] with h[8] = 1, over the inliers, in pixels.
+ *     Residuals r = (X/w - x', Y/w - y') with 1/w := 0 where |w| <= DBL_EPSILON.  Set-up: A = J^T J, v = J^T r, D = diag(A) taken
+ *     once, S = |r|^2, lambda = 1, lc = 0.75.  Each iteration:
+ *       a solve (A + lambda diag(D)) d = v by the symmetric eigen decomposition Q diag(e) Q^T (cyclic Jacobi); an eigenvalue with
+ *         |e_i| <= 2 DBL_EPSILON sum_j |e_j| is treated as zero (its direction contributes nothing to d);
+ *       b x_d = x - d;  S_d = |r(x_d)|^2;  dS = d^T (2 v - A d);  R = (S - S_d) / (|dS| > DBL_EPSILON ? dS : 1);
+ *       c R > 0.75: lambda *= 0.5, then lambda = 0 if lambda < lc;
+ *         else R < 0.25: nu = clamp((S_d - S) / (|d^T v| > DBL_EPSILON ? d^T v : 1) + 2, 2, 10); if lambda = 0:
+ *         lambda = lc = 1 / max(DBL_EPSILON, max_i |(A^-1)_ii|) (A^-1 by the same decomposition and zero rule) and nu *= 0.5;
+ *         lambda *= nu;
+ *       d S_d < S: accept, x = x_d, and r, J, A, v, S are recomputed;
+ *       e stop after 10 iterations, or when |d|_inf < FLT_EPSILON, or when |r|_inf < FLT_EPSILON (r of the kept x).
+ *     This loop is a restatement of OpenCV's LMSolver from memory; what is written here is the definition.
+ *
+ * dfepe_homography_transfer: evaluate_frontend.getInliers (deepFEPE/evaluate_frontend.py:210-228).  H [B,9] fp64; matches and
+ *   n_valid as above (N >= 0; B == 0 or N == 0: OK, nothing happens); dist [B,N] fp32 = |H x1 - x2| (the fp64 value of
+ *   sqrt(dx^2 + dy^2) after the division by w, rounded once; w = 0 gives what the division gives), mask [B,N] uint8 = dist < epi
+ *   on the fp64 value, with the reference's strict <.  Rows past n_valid get dist 0 and mask 0.  dist or mask may be NULL, not both.
+ * dfepe_homography_corners: the correctness test of descriptor_evaluation.compute_homography (lines 104-123).  H_est, H_gt
+ *   [B,9] fp64; the corners (0,0), (0,height-1), (width-1,0), (width-1,height-1) are warped by both, mean_dist [B] fp64 (or NULL)
+ *   is the mean of the four distances, correct [B,T] uint8 = mean_dist <= thresh[j] for the T thresholds in device memory
+ *   (thresh [T] fp64).  height, width >= 1, T >= 0 (T == 0: only mean_dist).  An all-zero H_est (no model) gives NaN and 0.
+ */
+#define DFEPE_HOMOGRAPHY_ALL_POINTS 1u /* cv2's method = 0: least squares over all points, then the refinement */
+#define DFEPE_HOMOGRAPHY_NO_REFINE 2u  /* no Levenberg-Marquardt step: H_out is the refit */
+
+size_t dfepe_homography_workspace_bytes(int B, int N, int max_iters);
+int dfepe_ransac_homography(const float *matches, const int *n_valid, int B, int N, double threshold, double confidence,
+                            int max_iters, unsigned long long seed, unsigned flags, void *workspace, double *H_out,
+                            double *H_model, unsigned char *inlier_mask, int *n_inliers, int *iters_run, int *best_iter,
+                            int *hyp_counts, void *stream);
+int dfepe_homography_transfer(const double *H, const float *matches, const int *n_valid, int B, int N, double epi, float *dist,
+                              unsigned char *mask, void *stream);
+int dfepe_homography_corners(const double *H_est, const double *H_gt, int B, int height, int width, const double *thresh, int T,
+                             double *mean_dist, unsigned char *correct, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

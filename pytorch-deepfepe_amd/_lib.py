@@ -35,6 +35,9 @@ LMEDS_MIN_N = 8  # dfepe_lmeds_fundamental: N = 7 is OpenCV's direct 7-point pat
 LMEDS5_MIN_N = 6  # dfepe_lmeds_essential
 POSE_CAMERA_MOTION = 1  # dfepe_two_view_structure / dfepe_reproject: Rt is camera motion (DFEPE_POSE_CAMERA_MOTION)
 RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked models of the one sample (not built)
+HOMOGRAPHY_ALL_POINTS = 1  # dfepe_ransac_homography: cv2's method = 0 (DFEPE_HOMOGRAPHY_ALL_POINTS)
+HOMOGRAPHY_NO_REFINE = 2  # ... no Levenberg-Marquardt step (DFEPE_HOMOGRAPHY_NO_REFINE)
+HOMOGRAPHY_MAX_N = 4096
 
 _P = c_void_p
 _SIGNATURES = {
@@ -127,6 +130,10 @@ _SIGNATURES = {
     "dfepe_triangulate": (c_int, [_P, c_int, _P, c_int, _P, c_int, c_int, _P, _P]),
     "dfepe_two_view_structure": (c_int, [_P, c_uint, _P, _P, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P]),
     "dfepe_reproject": (c_int, [_P, _P, c_int, c_uint, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
+    "dfepe_homography_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_ransac_homography": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, c_uint, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dfepe_homography_transfer": (c_int, [_P, _P, _P, c_int, c_int, c_double, _P, _P, _P]),
+    "dfepe_homography_corners": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -11,6 +11,9 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
                                                                     get_virt_x1x2*: the F-loss's virtual points, no cv2)
     deepFEPE.dsac_tools.utils_opencv    ->   compat.utils_opencv    (recover_camera_opencv: the 8-point RANSAC baseline, no cv2;
                                                                     triangulatePoints in place of cv2.triangulatePoints)
+                                                                    findHomography in place of cv2.findHomography)
+    evaluations.descriptor_evaluation   ->   compat.descriptor_evaluation (compute_homography, homography_estimation; getInliers
+                                                                    and getInliers_cv of deepFEPE/evaluate_frontend.py)
     deepFEPE.dsac_tools.utils_vis       ->   compat.utils_vis       (reproj_and_scatter without the drawing)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)
@@ -22,5 +25,7 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, dsac, eval_tools, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
+from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, dsac, eval_tools, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401
+from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
+from .utils_opencv import findHomography, findHomography_batch  # noqa: F401

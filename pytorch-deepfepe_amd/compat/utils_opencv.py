@@ -213,3 +213,37 @@ def KNN_match_batch(des1, des2, x1_all, x2_all, ratio=0.8, out_num_points=None):
     out["xs"] = xs
     out["quality"] = torch.cat((q, torch.gather(dist1 / dist2, 1, rows).unsqueeze(-1)), dim=2)
     return out
+
+
+# ---- cv2.findHomography ------------------------------------------------------------------------------------------------------
+RANSAC, LMEDS, RHO = 8, 4, 16  # cv2's method constants
+
+
+def findHomography_batch(matches, n_valid=None, method=RANSAC, ransacReprojThreshold=3.0, maxIters=2000, confidence=0.995, seed=0):
+    """cv2.findHomography for B pairs on the device: matches [B,N,4] (x1, y1, x2, y2), n_valid [B] int32 or None ->
+    (H [B,3,3] float64, zeros where cv2 returns None; mask [B,N] uint8; found [B] bool).  No host synchronisation."""
+    if method not in (0, RANSAC):
+        raise NotImplementedError(f"findHomography: method {method} (LMEDS = 4 and RHO = 16 are not built; 0 and RANSAC = 8 are)")
+    out = ops.ransac_homography(matches, n_valid, ransacReprojThreshold, confidence, maxIters, seed, all_points=(method == 0))
+    return out["H"], out["mask"], out["n_inliers"] > 0
+
+
+def findHomography(srcPoints, dstPoints, method=RANSAC, ransacReprojThreshold=3.0, maxIters=2000, confidence=0.995, seed=0):
+    """cv2.findHomography(srcPoints, dstPoints, method, ransacReprojThreshold, maxIters=, confidence=) with cv2's layout, numpy in
+    and out: points [N,2] (or [N,1,2]) -> (H float64 [3,3] or None when there is no model, mask uint8 [N,1]).  method 0 (least
+    squares over all points) and 8 (RANSAC) are built; LMEDS (4) and RHO (16) raise NotImplementedError.  What differs from
+    OpenCV: the random stream (`seed`; include/dfepe.h, dfepe_ransac_homography), so results agree with cv2's in distribution,
+    not bit for bit.  evaluations/descriptor_evaluation.py:93, deepFEPE/evaluate_frontend.py:234."""
+    if method not in (0, RANSAC):
+        raise NotImplementedError(f"findHomography: method {method} (LMEDS = 4 and RHO = 16 are not built; 0 and RANSAC = 8 are)")
+    src = np.asarray(srcPoints, dtype=np.float32).reshape(-1, 2)
+    dst = np.asarray(dstPoints, dtype=np.float32).reshape(-1, 2)
+    if src.shape != dst.shape:
+        raise ValueError(f"srcPoints and dstPoints must hold the same number of points, got {src.shape} and {dst.shape}")
+    N = src.shape[0]
+    if N < 4:
+        return None, np.zeros((N, 1), dtype=np.uint8)
+    m = torch.as_tensor(np.ascontiguousarray(np.hstack((src, dst))), device=torch.device("cuda")).unsqueeze(0)
+    H, mask, found = findHomography_batch(m, None, method, ransacReprojThreshold, maxIters, confidence, seed)
+    mask = mask[0].cpu().numpy().reshape(N, 1)
+    return (H[0].cpu().numpy() if bool(found[0]) else None), mask

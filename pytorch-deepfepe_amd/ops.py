@@ -1590,3 +1590,97 @@ def gather_matches(pts1: Tensor, pts2: Tensor, off1: Optional[Tensor], off2: Opt
                                              _ptr(choice), n_out, _ptr(xs), _ptr(offs), _ptr(q), _stream())
     _lib.check(rc, "dfepe_gather_matches")
     return xs, offs, q
+
+
+def _n_valid_arg(n_valid, B: int, dev, name: str) -> Optional[Tensor]:
+    if n_valid is None:
+        return None
+    if not torch.is_tensor(n_valid) or not n_valid.is_cuda:
+        raise _lib.DfepeError(f"{name}: n_valid must be an int32 [B] tensor on the GPU (the counts stay on the device)")
+    if n_valid.shape != (B,):
+        raise ValueError(f"{name}: n_valid must have shape [{B}], got {tuple(n_valid.shape)}")
+    return n_valid.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _h9(H: Tensor, name: str, B: int) -> Tensor:
+    if not H.is_cuda:
+        raise _lib.DfepeError(f"{name} must live on the GPU (this package has no CPU path)")
+    if H.shape not in ((B, 3, 3), (B, 9)):
+        raise ValueError(f"{name} must have shape [{B},3,3], got {tuple(H.shape)}")
+    return H.to(torch.float64).contiguous()
+
+
+def ransac_homography(matches: Tensor, n_valid: Optional[Tensor] = None, threshold: float = 3.0, confidence: float = 0.995,
+                      max_iters: int = 2000, seed: int = 0, refine: bool = True, all_points: bool = False,
+                      want_hyp_counts: bool = False, want_model: bool = False) -> dict:
+    """matches [B,N,4] pixels (x1, y1, x2, y2) -> robust homography of every pair by OpenCV 3.4's findHomography(RANSAC) algorithm
+    (descriptor_evaluation.py:93, evaluate_frontend.py:234; include/dfepe.h spells out the sampler, the 4-point solve, the error,
+    the stopping rule, the refit over the inliers and the Levenberg-Marquardt refinement).  n_valid [B] int32 on the device or
+    None: pair b uses its first n_valid[b] rows.  all_points: cv2's method = 0 (least squares over all points, mask all ones);
+    refine=False leaves out the refinement.  Returns dict(H [B,3,3] float64 (H22 = 1; zeros without a model), mask [B,N] uint8,
+    n_inliers [B], iters_run [B], best_iter [B] (-1 without a sampled winner), hyp_counts [B,max_iters] | None (-1: no model,
+    -2: no sample), H_model [B,3,3] float64 | None (the winning sample's H before the refit)).  No host synchronisation;
+    capturable.  1 <= N <= 4096."""
+    m = _prep(matches, "matches")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    B, N = m.shape[0], m.shape[1]
+    if N < 1 or N > _lib.HOMOGRAPHY_MAX_N:
+        raise _lib.DfepeError(f"ransac_homography: {N} correspondences per pair; the estimator takes 1 .. {_lib.HOMOGRAPHY_MAX_N}")
+    L = _lib.lib()
+    dev = m.device
+    nv = _n_valid_arg(n_valid, B, dev, "ransac_homography")
+    flags = (_lib.HOMOGRAPHY_ALL_POINTS if all_points else 0) | (0 if refine else _lib.HOMOGRAPHY_NO_REFINE)
+    ws = torch.empty(max(1, (int(L.dfepe_homography_workspace_bytes(B, N, int(max_iters))) + 15) // 16), 2, dtype=torch.float64, device=dev)
+    out = {
+        "H": torch.empty(B, 3, 3, device=dev, dtype=torch.float64),
+        "mask": torch.empty(B, N, device=dev, dtype=torch.uint8),
+        "n_inliers": torch.empty(B, device=dev, dtype=torch.int32),
+        "iters_run": torch.empty(B, device=dev, dtype=torch.int32),
+        "best_iter": torch.empty(B, device=dev, dtype=torch.int32),
+        "hyp_counts": torch.empty(B, int(max_iters), device=dev, dtype=torch.int32) if want_hyp_counts else None,
+        "H_model": torch.empty(B, 3, 3, device=dev, dtype=torch.float64) if want_model else None,
+    }
+    with _on(dev):
+        rc = L.dfepe_ransac_homography(_ptr(m), _ptr(nv), B, N, float(threshold), float(confidence), int(max_iters), int(seed) & ((1 << 64) - 1),
+                                       flags, _ptr(ws), _ptr(out["H"]), _ptr(out["H_model"]), _ptr(out["mask"]), _ptr(out["n_inliers"]),
+                                       _ptr(out["iters_run"]), _ptr(out["best_iter"]), _ptr(out["hyp_counts"]), _stream())
+    _lib.check(rc, "dfepe_ransac_homography")
+    return out
+
+
+def homography_transfer(H: Tensor, matches: Tensor, n_valid: Optional[Tensor] = None, epi: float = 3.0):
+    """H [B,3,3], matches [B,N,4] -> (dist [B,N] fp32 = |H x1 - x2|, mask [B,N] uint8 = dist < epi): evaluate_frontend.getInliers
+    (evaluate_frontend.py:210-228) for B pairs, evaluated in fp64.  Rows past n_valid get 0 and 0.  No host synchronisation."""
+    m = _prep(matches, "matches")
+    _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+    B, N = m.shape[0], m.shape[1]
+    Hd = _h9(H, "H", B)
+    dev = m.device
+    nv = _n_valid_arg(n_valid, B, dev, "homography_transfer")
+    dist = torch.empty(B, N, device=dev)
+    mask = torch.empty(B, N, device=dev, dtype=torch.uint8)
+    with _on(dev):
+        rc = _lib.lib().dfepe_homography_transfer(_ptr(Hd), _ptr(m), _ptr(nv), B, N, float(epi), _ptr(dist), _ptr(mask), _stream())
+    _lib.check(rc, "dfepe_homography_transfer")
+    return dist, mask
+
+
+def homography_corners(H_est: Tensor, H_gt: Tensor, height: int, width: int, thresh: Tensor):
+    """H_est, H_gt [B,3,3]; thresh [T] on the device -> (mean_dist [B] float64, correct [B,T] uint8): the mean distance of the
+    four image corners warped by both homographies and `mean_dist <= thresh` (descriptor_evaluation.compute_homography, lines
+    104-123).  An all-zero H_est (no model) gives NaN and 0.  No host synchronisation."""
+    if not H_est.is_cuda:
+        raise _lib.DfepeError("H_est must live on the GPU (this package has no CPU path)")
+    B = H_est.shape[0]
+    He, Hg = _h9(H_est, "H_est", B), _h9(H_gt, "H_gt", B)
+    dev = He.device
+    if not torch.is_tensor(thresh) or not thresh.is_cuda or thresh.dim() != 1:
+        raise _lib.DfepeError("homography_corners: thresh must be a 1-D tensor on the GPU")
+    th = thresh.to(torch.float64).contiguous()
+    T = th.shape[0]
+    md = torch.empty(B, device=dev, dtype=torch.float64)
+    ok = torch.empty(B, T, device=dev, dtype=torch.uint8)
+    with _on(dev):
+        rc = _lib.lib().dfepe_homography_corners(_ptr(He), _ptr(Hg), B, int(height), int(width), _ptr(th), T, _ptr(md), _ptr(ok), _stream())
+    _lib.check(rc, "dfepe_homography_corners")
+    return md, ok
