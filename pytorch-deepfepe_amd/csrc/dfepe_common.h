@@ -111,4 +111,20 @@ __device__ __forceinline__ Pt global_point(const float* __restrict__ pts1, const
   return p;
 }
 
+// ---- host side of a launch ------------------------------------------------------------------
+constexpr int kMaxGridY = 65535;  // pairs go on the grid's y dimension
+inline int launched() { return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Dynamic LDS above the 64 KiB a kernel gets by default has to be asked for per kernel.  false: the runtime refused.
+template <class Kernel>
+inline bool opt_in_lds(Kernel kernel, size_t bytes) {
+  return bytes <= 65536 ||
+         hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+
+// Workspace of a RANSAC estimator: the B winners in fp64 (9 doubles each), then the [B, max_iters, slots] table.
+inline size_t robust_workspace_bytes(int B, int max_iters, int slots, size_t entry) {
+  if (B <= 0 || max_iters <= 0) return 0;
+  return (size_t)B * 9 * sizeof(double) + (size_t)B * max_iters * slots * entry;
+}

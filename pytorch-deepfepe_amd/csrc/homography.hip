@@ -8,20 +8,20 @@
 //           and half the LDS of staged doubles), one lane of wavefront 0 per iteration draws its sample and solves the 4-point
 //           system in fp64, then the four wavefronts share the 64 hypotheses and sweep all correspondences for each (__ballot /
 //           __popcll); the counts go to the [B, max_iters] table.  Every iteration is evaluated; select reads what the rule reads.
-//   select  one wavefront per pair: the sequential rule over the table (a ballot finds each model the rule takes), then lane 0
-//           draws and solves the winning sample again with the same device functions (same H bit for bit).
+//   select  one wavefront per pair: the sequential rule over the table (select_wave, robust_dev.h, with one slot an iteration),
+//           then lane 0 solves the winning iteration again by the two halves of the count launch's hg::solve_iteration (same H
+//           bit for bit); a pair of exactly four points goes to the second half with its own points.
 //   mask    one lane per correspondence: the winner's inlier mask.
 //   refine  one wavefront per pair: runKernel over the inliers and the Levenberg-Marquardt refinement.  Lanes stride the
 //           correspondences under the mask (no compaction); every sum is a wavefront reduction in fp64; the 9x9 and 8x8 Jacobi
 //           decompositions run on lane 0 over matrices kept in LDS (profiles/homography.md).
-#include "dfepe_common.h"
 #include "homography_math.h"
+#include "robust_dev.h"
 
 namespace {
 
 constexpr int kChunk = 64;        // iterations per workgroup of the count launch (one hypothesis each)
 constexpr int kMaxN = 4096;       // correspondences staged in LDS (16 B each)
-constexpr int kMaxPairs = 65535;  // pairs go on the grid's y dimension
 constexpr unsigned kAllPoints = DFEPE_HOMOGRAPHY_ALL_POINTS, kNoRefine = DFEPE_HOMOGRAPHY_NO_REFINE;
 
 __device__ inline int pair_count(const int* __restrict__ n_valid, size_t pair, int N) {
@@ -52,24 +52,8 @@ __global__ void __launch_bounds__(256) homography_count_kernel(const float4* __r
     const int k = k0 + lane;
     int st = 0;
     if (k < max_iters) {
-      int idx[hg::kSample];
       auto pts = [&](int i) { return lds_pts[i]; };
-      if (hg::draw_sample4(seed, k, n, pts, idx)) {
-        float x1[hg::kSample], y1[hg::kSample], x2[hg::kSample], y2[hg::kSample];
-#pragma unroll
-        for (int i = 0; i < hg::kSample; ++i) {
-          const float4 m = lds_pts[idx[i]];
-          x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
-        }
-        double H[9];
-        st = hg::solve4(x1, y1, x2, y2, H) ? 1 : 0;
-        if (st) {
-#pragma unroll
-          for (int j = 0; j < 9; ++j) hypH[lane * 9 + j] = H[j];
-        }
-      } else {
-        st = rs::kNoSample;
-      }
+      st = hg::solve_iteration(seed, k, n, pts, hypH + lane * 9);  // the model goes straight to its slot; read only where st == 1
     }
     status[lane] = st;
   }
@@ -99,38 +83,6 @@ __global__ void __launch_bounds__(256) homography_count_kernel(const float4* __r
   }
 }
 
-// hg::select_best (the sequential definition) with one wavefront: the table is read 64 iterations at a time, one lane per
-// iteration, and the next model the sequential loop would take -- the first entry past the last one taken, of an iteration the
-// loop still reaches, whose count beats max(best, 3), or the first iteration without a sample -- is found by a ballot.
-__device__ inline int select_wave(const int* __restrict__ tab, int n, double confidence, int max_iters, int* best_k, int* iters) {
-  const int lane = threadIdx.x & 63;
-  int best = 0, niters = max_iters, bk = -1, stop = -1;
-  for (int base = 0; base < max_iters && stop < 0; base += 64) {
-    if (base >= niters) break;
-    const int k = base + lane;
-    const bool have = k < max_iters;
-    const int c = have ? tab[k] : rs::kNoRoot;
-    for (;;) {
-      const int thr = best > hg::kSample - 1 ? best : hg::kSample - 1;
-      const bool reached = have && k < niters && k > bk;
-      const unsigned long long hit = __ballot(reached && (c == rs::kNoSample || c > thr));
-      if (hit == 0ull) break;
-      const int L = __ffsll((long long)hit) - 1;
-      const int cL = __shfl(c, L, 64);
-      if (cL == rs::kNoSample) {
-        stop = base + L;
-        break;
-      }
-      best = cL;
-      bk = base + L;
-      niters = hg::update_num_iters4(confidence, (double)(n - cL) / n, niters);
-    }
-  }
-  *best_k = bk;
-  *iters = stop >= 0 ? stop : (niters > bk + 1 ? niters : bk + 1);
-  return best;
-}
-
 __global__ void __launch_bounds__(256) homography_select_kernel(const float4* __restrict__ matches, const int* __restrict__ n_valid, int B,
                                                                 int N, const int* __restrict__ table, double confidence, int max_iters,
                                                                 unsigned long long seed, unsigned flags, double* __restrict__ Hd,
@@ -140,27 +92,19 @@ __global__ void __launch_bounds__(256) homography_select_kernel(const float4* __
   if (b >= B) return;
   const int n = pair_count(n_valid, b, N);
   const bool sampled = n > hg::kSample && !(flags & kAllPoints);
-  int bk = -1, it = 0, best = 0;
-  if (sampled) best = select_wave(table + (size_t)b * max_iters, n, confidence, max_iters, &bk, &it);
+  int bk = -1, br, it = 0, best = 0;  // br: the one slot, not reported
+  if (sampled) best = select_wave<1, hg::kSample>(table + (size_t)b * max_iters, n, confidence, max_iters, &bk, &br, &it);
   if ((threadIdx.x & 63) != 0) return;
   double Hw[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j) Hw[j] = 0.0;
   const float4* mrow = matches + (size_t)b * N;
   if (n == hg::kSample || (sampled && bk >= 0)) {
-    int idx[hg::kSample] = {0, 1, 2, 3};
-    if (sampled) {
-      auto pts = [&](int i) { return mrow[i]; };
-      hg::draw_sample4(seed, bk, n, pts, idx);  // succeeded in the count launch: same stream, same sample
-    }
-    float x1[hg::kSample], y1[hg::kSample], x2[hg::kSample], y2[hg::kSample];
-#pragma unroll
-    for (int i = 0; i < hg::kSample; ++i) {
-      const float4 m = mrow[idx[i]];
-      x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
-    }
+    auto pts = [&](int i) { return mrow[i]; };
+    int idx[hg::kSample] = {0, 1, 2, 3};  // the pair's own four points, unless an iteration won:
+    if (sampled) hg::draw_sample4(seed, bk, n, pts, idx);  // it gave a sample in the count launch: same stream, same sample
     double H[9];
-    const bool ok = hg::solve4(x1, y1, x2, y2, H);
+    const bool ok = hg::solve_sample(pts, idx, H);  // the two halves of hg::solve_iteration, so that solve4 is inlined once
     if (ok) {
 #pragma unroll
       for (int j = 0; j < 9; ++j) Hw[j] = H[j];
@@ -327,15 +271,11 @@ __global__ void __launch_bounds__(256) homography_corners_kernel(const double* _
   for (int j = 0; j < T; ++j) correct[(size_t)b * T + j] = (md <= thresh[j]) ? 1 : 0;
 }
 
-int launched() { return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" size_t dfepe_homography_workspace_bytes(int B, int N, int max_iters) {
   (void)N;
-  if (B <= 0 || max_iters <= 0) return 0;
-  return (size_t)B * 9 * sizeof(double) + (size_t)B * max_iters * sizeof(int);
+  return robust_workspace_bytes(B, max_iters, 1, sizeof(int));
 }
 
 extern "C" int dfepe_ransac_homography(const float* matches, const int* n_valid, int B, int N, double threshold, double confidence,
@@ -345,7 +285,7 @@ extern "C" int dfepe_ransac_homography(const float* matches, const int* n_valid,
   if (B < 0 || N < 1 || max_iters < 1 || threshold != threshold || !(confidence >= 0.0 && confidence <= 1.0)) return DFEPE_ERR_INVALID_ARG;
   if (flags & ~(kAllPoints | kNoRefine)) return DFEPE_ERR_INVALID_ARG;
   if (B == 0) return DFEPE_OK;
-  if (N > kMaxN || B > kMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (N > kMaxN || B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   if (!matches || !workspace || !H_out || !inlier_mask || !n_inliers || !iters_run) return DFEPE_ERR_INVALID_ARG;
   if (!aligned16(matches) || !aligned16(workspace)) return DFEPE_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -356,9 +296,7 @@ extern "C" int dfepe_ransac_homography(const float* matches, const int* n_valid,
   const float4* m4 = reinterpret_cast<const float4*>(matches);
   if (!(flags & kAllPoints)) {
     const size_t lds = (size_t)N * sizeof(float4) + (size_t)kChunk * 9 * sizeof(double) + (size_t)2 * kChunk * sizeof(int);
-    if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(homography_count_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return DFEPE_ERR_HIP;
+    if (!opt_in_lds(homography_count_kernel, lds)) return DFEPE_ERR_HIP;
     hipLaunchKernelGGL(homography_count_kernel, dim3((max_iters + kChunk - 1) / kChunk, B), dim3(256), lds, s, m4, n_valid, N,
                        max_iters, t2, seed, table);
   }
@@ -375,7 +313,7 @@ extern "C" int dfepe_homography_transfer(const double* H, const float* matches, 
                                          float* dist, unsigned char* mask, void* stream) {
   if (B < 0 || N < 0 || epi != epi) return DFEPE_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return DFEPE_OK;
-  if (B > kMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   if (!H || !matches || (!dist && !mask) || !aligned16(matches)) return DFEPE_ERR_INVALID_ARG;
   hipLaunchKernelGGL(homography_transfer_kernel, dim3((N + 255) / 256, B), dim3(256), 0, static_cast<hipStream_t>(stream), H,
                      reinterpret_cast<const float4*>(matches), n_valid, N, epi, dist, mask);

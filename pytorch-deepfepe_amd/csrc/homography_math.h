@@ -4,7 +4,7 @@
 // reference calls in evaluations/descriptor_evaluation.py:93 and deepFEPE/evaluate_frontend.py:234; the contract is spelled out
 // in include/dfepe.h (dfepe_ransac_homography).  The stream, the Lemire map and the count-table codes are those of ransac_math.h.
 //
-// Two kinds of code live here.  Pure functions of their arguments (sampling, the 4-point solve, the error, the rule), and the
+// Two kinds of code live here.  Pure functions of their arguments (sampling, the 4-point solve, the error), and the
 // refit / refinement drivers, which are templates over a context Ctx that supplies the sums over a pair's inliers:
 //   ctx.reduce(kind, par, out)  fills out[0 .. 45] with the sums of `kind` over the inliers (out[45]: a maximum), same in every lane
 //   ctx.leader()                whether this lane does the small dense algebra (the host: always; the device: lane 0)
@@ -20,18 +20,6 @@ constexpr int kSample = 4;  // points per minimal sample
 constexpr int kLmIters = 10;
 constexpr int kSweeps = 50;  // cyclic Jacobi: sweeps at most (9x9 and 8x8 converge in 6..9)
 constexpr int kRed = 46;     // reduction record: 45 sums and one maximum
-
-// OpenCV's RANSACUpdateNumIters(p, ep, 4, niters): rs::update_num_iters is hard-wired to 7 model points; this is its twin.
-RS_HD int update_num_iters4(double p, double ep, int niters) {
-  p = fmin(fmax(p, 0.0), 1.0);
-  ep = fmin(fmax(ep, 0.0), 1.0);
-  const double num = fmax(1.0 - p, DBL_MIN);
-  const double q = 1.0 - ep, q2 = q * q;
-  const double den = 1.0 - q2 * q2;
-  if (den < DBL_MIN) return 0;
-  const double ln = log(num), ld = log(den);
-  return (ld >= 0.0 || -ln >= niters * (-ld)) ? niters : (int)rint(ln / ld);
-}
 
 // rs::collinear_last for a sample of 4: the last point against every line through two earlier ones.
 RS_HD bool collinear_last4(const float* x, const float* y) {
@@ -198,23 +186,35 @@ RS_HD bool is_inlier(const double* H, double x1, double y1, double x2, double y2
   return (w != 0.0) && (dx * dx + dy * dy <= t2 * (w * w));
 }
 
-// The sequential selection rule over one pair's count table counts[k] (k < max_iters; rs::kNoRoot = the solve gave no model,
-// rs::kNoSample = no sample).  Returns the best count (0: no model); *best_k the winning iteration or -1; *iters the k the
-// loop stopped at.  The select launch evaluates the same rule a wavefront at a time (csrc/homography.hip).
-RS_HD int select_best(const int* counts, int N, double confidence, int max_iters, int* best_k, int* iters) {
-  int best = 0, niters = max_iters, k = 0;
-  *best_k = -1;
-  for (; k < niters; ++k) {
-    const int c = counts[k];
-    if (c == rs::kNoSample) break;
-    if (c > (best > kSample - 1 ? best : kSample - 1)) {
-      best = c;
-      *best_k = k;
-      niters = update_num_iters4(confidence, (double)(N - c) / N, niters);
-    }
+// The gather-and-solve half of an iteration: solve4 on the four correspondences idx of a pair (P as in draw_sample4).  The pair
+// of exactly four points comes here directly with idx = {0, 1, 2, 3}.
+template <class P>
+RS_HD bool solve_sample(const P& pts, const int* idx, double* H) {
+  float x1[kSample], y1[kSample], x2[kSample], y2[kSample];
+#pragma unroll
+  for (int i = 0; i < kSample; ++i) {
+    const auto m = pts(idx[i]);
+    x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
   }
-  *iters = k;
-  return best;
+  return solve4(x1, y1, x2, y2, H);
+}
+
+// Iteration k of a pair, whole: its sample drawn, gathered and solved.  The count launch calls this and the select launch its
+// two halves (so that the pair of four points can enter at the second), which is what makes the winner come out again bit for
+// bit.  1: H holds the model; 0: the solve gave none (rs::kNoRoot in the count table); rs::kNoSample: no sample.
+template <class P>
+RS_HD int solve_iteration(uint64_t seed, int k, int n, const P& pts, double* H) {
+  int idx[kSample];
+  if (!draw_sample4(seed, k, n, pts, idx)) return rs::kNoSample;
+  return solve_sample(pts, idx, H) ? 1 : 0;
+}
+
+// The iteration bound and the sequential selection rule over one pair's count table counts[k] (rs::kNoRoot = the solve gave no
+// model, rs::kNoSample = no sample) are ransac_math.h's, with 4 points and one slot an iteration (so no best root to report).
+RS_HD int update_num_iters4(double p, double ep, int niters) { return rs::update_num_iters<kSample>(p, ep, niters); }
+RS_HD int select_best(const int* counts, int N, double confidence, int max_iters, int* best_k, int* iters) {
+  int slot;
+  return rs::select_best<1, kSample>(counts, N, confidence, max_iters, best_k, &slot, iters);
 }
 
 // ---- sums over the inliers: what one correspondence adds to the record acc[kRed] ------------------------------------------

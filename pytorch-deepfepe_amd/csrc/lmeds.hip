@@ -28,7 +28,6 @@ constexpr int kChunkL = 16;      // iterations per workgroup of the median launc
 constexpr int kMaxNL = 4096;     // correspondences staged in LDS (16 B each); 64 lanes x 64 registers
 constexpr int kMinNF = 8;        // N = 7 is OpenCV's direct 7-point path (not built)
 constexpr int kMinNE = 6;        // N = 5: the stacked models of the one sample (not built)
-constexpr int kMaxPairsL = 65535;
 constexpr int kSelectWavesL = 4;
 
 __device__ inline int wave_sum(int x) {
@@ -53,12 +52,6 @@ struct DevWave {
   __device__ int sum(F f) const { return wave_sum(f(v)); }
   template <class F>
   __device__ int max(F f) const { return wave_max(f(v)); }
-};
-
-template <int S>
-struct LaneWorkL {
-  double* p;
-  __device__ double& operator[](int i) const { return p[i * S]; }
 };
 
 struct ModelF {
@@ -89,21 +82,12 @@ __global__ void __launch_bounds__(256) lmeds_median_f_kernel(const float4* __res
     const int k = k0 + tid;
     int n = 0;
     if (k < niters) {
-      int idx[rs::kSample];
       auto pts = [&](int i) { return lds_ptsl[i]; };
-      if (rs::draw_sample(seed, k, N, pts, idx)) {
-        float x1[rs::kSample], y1[rs::kSample], x2[rs::kSample], y2[rs::kSample];
-#pragma unroll
-        for (int i = 0; i < rs::kSample; ++i) {
-          const float4 m = lds_ptsl[idx[i]];
-          x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
-        }
-        double F[9 * rs::kMaxRoots];
-        n = rs::seven_point(x1, y1, x2, y2, F);
+      double F[9 * rs::kMaxRoots];
+      n = rs::solve_iteration(seed, k, N, pts, F);
+      if (n != rs::kNoSample) {
 #pragma unroll
         for (int j = 0; j < 9 * rs::kMaxRoots; ++j) hypF[tid * 9 * rs::kMaxRoots + j] = F[j];
-      } else {
-        n = rs::kNoSample;
       }
     }
     nroots[tid] = n;
@@ -140,19 +124,6 @@ __global__ void __launch_bounds__(256) lmeds_median_f_kernel(const float4* __res
 }
 
 // ---- median launch, essential matrix --------------------------------------------------------------------------------------
-template <class W, class P>
-__device__ inline int solve_iteration5(W& w, const P& pts, const r5::Cam& cam, unsigned long long seed, int k, int N) {
-  int idx[r5::kSample];
-  r5::draw_sample(seed, k, N, idx);
-  double x1[r5::kSample], y1[r5::kSample], x2[r5::kSample], y2[r5::kSample];
-#pragma unroll
-  for (int i = 0; i < r5::kSample; ++i) {
-    const float4 m = pts(idx[i]);
-    x1[i] = r5::norm_x(cam, m.x); y1[i] = r5::norm_y(cam, m.y); x2[i] = r5::norm_x(cam, m.z); y2[i] = r5::norm_y(cam, m.w);
-  }
-  return r5::five_point(w, x1, y1, x2, y2);
-}
-
 template <int R>
 __global__ void __launch_bounds__(256) lmeds_median_e_kernel(const float4* __restrict__ matches, const float* __restrict__ K, int N, int niters,
                                                              unsigned long long seed, double* __restrict__ table) {
@@ -172,9 +143,9 @@ __global__ void __launch_bounds__(256) lmeds_median_e_kernel(const float4* __res
     const int k = k0 + tid;
     int n = 0;
     if (k < niters) {
-      LaneWorkL<kChunkL> w{work + tid};
+      r5::LaneWork<kChunkL> w{work + tid};
       auto pts = [&](int i) { return lds_ptsl[i]; };
-      n = solve_iteration5(w, pts, cam, seed, k, N);
+      n = r5::solve_iteration(w, pts, cam, seed, k, N);
     }
     nroots[tid] = n;
   }
@@ -291,16 +262,8 @@ __global__ void __launch_bounds__(64 * kSelectWavesL) lmeds_select_f_kernel(cons
   for (int j = 0; j < 9; ++j) Fw[j] = 0.0;
   if (bk >= 0 && (threadIdx.x & 63) == 0) {
     auto pts = [&](int i) { return mrow[i]; };
-    int idx[rs::kSample];
-    rs::draw_sample(seed, bk, N, pts, idx);  // succeeded in the median launch: same stream, same sample
-    float x1[rs::kSample], y1[rs::kSample], x2[rs::kSample], y2[rs::kSample];
-#pragma unroll
-    for (int i = 0; i < rs::kSample; ++i) {
-      const float4 m = mrow[idx[i]];
-      x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
-    }
     double F[9 * rs::kMaxRoots];
-    rs::seven_point(x1, y1, x2, y2, F);
+    rs::solve_iteration(seed, bk, N, pts, F);  // gave a sample in the median launch: same stream, same sample, same roots
 #pragma unroll
     for (int r = 0; r < rs::kMaxRoots; ++r)
       if (r == br) {
@@ -333,8 +296,8 @@ __global__ void __launch_bounds__(64 * kSelectWavesL) lmeds_select_e_kernel(cons
   for (int j = 0; j < 9; ++j) Ew[j] = 0.0;
   if (bk >= 0 && (threadIdx.x & 63) == 0) {
     auto pts = [&](int i) { return mrow[i]; };
-    LaneWorkL<1> w{work[wave]};
-    solve_iteration5(w, pts, cam, seed, bk, N);  // same stream, same sample, same solutions
+    r5::LaneWork<1> w{work[wave]};
+    r5::solve_iteration(w, pts, cam, seed, bk, N);  // same stream, same sample, same solutions
 #pragma unroll
     for (int j = 0; j < 9; ++j) Ew[j] = w[r5::kOffE + 9 * br + j];
   }
@@ -375,8 +338,6 @@ __global__ void __launch_bounds__(256) lmeds_mask_kernel(const float4* __restric
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 size_t lds_bytes(int N, bool essential) {
   const size_t models = essential ? (size_t)r5::kWork * kChunkL * sizeof(double) : (size_t)kChunkL * rs::kMaxRoots * 9 * sizeof(double);
   const size_t hyps = (size_t)kChunkL * (essential ? r5::kMaxRoots : rs::kMaxRoots);
@@ -388,7 +349,7 @@ int launch_median(bool essential, const float4* m4, const float* K, int B, int N
                   hipStream_t s) {
   const size_t lds = lds_bytes(N, essential);
   const void* fn = essential ? reinterpret_cast<const void*>(lmeds_median_e_kernel<R>) : reinterpret_cast<const void*>(lmeds_median_f_kernel<R>);
-  if (lds > 65536 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return DFEPE_ERR_HIP;
+  if (!opt_in_lds(fn, lds)) return DFEPE_ERR_HIP;
   const dim3 grid((niters + kChunkL - 1) / kChunkL, B);
   if (essential)
     hipLaunchKernelGGL(lmeds_median_e_kernel<R>, grid, dim3(256), lds, s, m4, K, N, niters, seed, table);
@@ -402,7 +363,7 @@ int run_lmeds(bool essential, const float* matches, const float* K, int B, int N
               double* sigma, double* hyp_medians, float* masked_matches, void* stream) {
   if (B < 0 || max_iters <= 0 || !(confidence >= 0.0 && confidence <= 1.0)) return DFEPE_ERR_INVALID_ARG;
   if (B == 0) return DFEPE_OK;
-  if (N < (essential ? kMinNE : kMinNF) || N > kMaxNL || B > kMaxPairsL) return DFEPE_ERR_UNSUPPORTED;
+  if (N < (essential ? kMinNE : kMinNF) || N > kMaxNL || B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   if (!matches || (essential && !K) || !workspace || !M_out || !inlier_mask || !n_inliers || !iters_run) return DFEPE_ERR_INVALID_ARG;
   if (!aligned16(matches) || !aligned16(workspace) || (masked_matches && !aligned16(masked_matches))) return DFEPE_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -434,7 +395,7 @@ int run_lmeds(bool essential, const float* matches, const float* K, int B, int N
     hipLaunchKernelGGL(lmeds_select_f_kernel, sgrid, sblock, 0, s, m4, B, N, table, niters, seed, o);
     hipLaunchKernelGGL(lmeds_mask_kernel<false>, dim3((N + 255) / 256, B), dim3(256), 0, s, m4, K, N, Md, bound, n_inliers, inlier_mask, masked);
   }
-  return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
+  return launched();
 }
 
 }  // namespace

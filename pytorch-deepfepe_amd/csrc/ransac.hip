@@ -9,13 +9,11 @@
 //           into LDS), then the four wavefronts share the hypotheses and sweep all correspondences for each (fp64 inlier test,
 //           __ballot / __popcll); the counts go to the [B, max_iters, 3] table.  Every iteration is evaluated, also those beyond
 //           the stopping point the sequential rule will find: the select launch reads only what the rule reads.
-//   select  one wavefront per pair: the sequential rule over the table (a ballot finds each model the rule takes), then the
-//           winning sample drawn and solved again by the same device functions (same F bit for bit, no hypothesis storage).
-//   mask    one lane per correspondence: the winner's inlier mask, and optionally a copy of the matches with the other rows
-//           set to quiet NaN (the masked input of the unchanged cheirality kernel: a NaN row passes no depth test).
+//   select  one wavefront per pair: the sequential rule over the table (select_wave, robust_dev.h), then the winning iteration
+//           solved again by rs::solve_iteration, as the count launch solved it (same F bit for bit, no hypothesis storage).
+//   mask    robust_dev.h's mask_kernel around rs::is_inlier.
 #include "cheirality_body.h"
-#include "dfepe_common.h"
-#include "ransac_math.h"
+#include "robust_dev.h"
 
 namespace {
 
@@ -23,7 +21,6 @@ constexpr int kChunk = 64;                        // iterations per workgroup of
 constexpr int kHyps = kChunk * rs::kMaxRoots;     // hypotheses per workgroup
 constexpr int kMaxN = 4096;                       // correspondences staged in LDS (16 B each)
 constexpr int kMinN = 15;                         // below: OpenCV switches to LMedS (lmeds.hip)
-constexpr int kMaxPairs = 65535;                  // pairs go on the grid's y dimension
 
 __global__ void __launch_bounds__(256) ransac_count_kernel(const float4* __restrict__ matches, int N, int max_iters, double t2,
                                                            unsigned long long seed, int* __restrict__ table) {
@@ -41,21 +38,12 @@ __global__ void __launch_bounds__(256) ransac_count_kernel(const float4* __restr
     const int k = k0 + lane;
     int n = 0;
     if (k < max_iters) {
-      int idx[rs::kSample];
       auto pts = [&](int i) { return lds_pts[i]; };
-      if (rs::draw_sample(seed, k, N, pts, idx)) {
-        float x1[rs::kSample], y1[rs::kSample], x2[rs::kSample], y2[rs::kSample];
-#pragma unroll
-        for (int i = 0; i < rs::kSample; ++i) {
-          const float4 m = lds_pts[idx[i]];
-          x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
-        }
-        double F[9 * rs::kMaxRoots];
-        n = rs::seven_point(x1, y1, x2, y2, F);
+      double F[9 * rs::kMaxRoots];
+      n = rs::solve_iteration(seed, k, N, pts, F);
+      if (n != rs::kNoSample) {
 #pragma unroll
         for (int j = 0; j < 9 * rs::kMaxRoots; ++j) hypF[lane * 27 + j] = F[j];
-      } else {
-        n = rs::kNoSample;
       }
     }
     nroots[lane] = n;
@@ -92,51 +80,6 @@ __global__ void __launch_bounds__(256) ransac_count_kernel(const float4* __restr
   }
 }
 
-// rs::select_best (the sequential definition) with one wavefront per pair: the table is read 64 iterations at a time, one lane
-// per iteration, and the next model the sequential loop would take -- the first entry, in (k, root) order, past the last one
-// taken, of an iteration the loop still reaches, whose count beats max(best, 6), or the first iteration without a sample -- is
-// found by a ballot.  Same results as rs::select_best (tests/test_ransac_gpu.py holds the outputs to tests/ransac_ref.py's rule);
-// one lane doing it alone spent ~400 us in dependent global loads (rocprofv3, 8 pairs x 1000 iterations).
-__device__ inline int select_wave(const int* __restrict__ tab, int N, double confidence, int max_iters, int* best_k, int* best_r, int* iters) {
-  const int lane = threadIdx.x & 63;
-  int best = 0, niters = max_iters, bk = -1, br = -1, done = -1, stop = -1;  // done: last entry (3 k + r) taken
-  for (int base = 0; base < max_iters && stop < 0; base += 64) {
-    if (base >= niters) break;  // no iteration from here on is reached (bk < base)
-    const int k = base + lane;
-    const bool have = k < max_iters;
-    const int c0 = have ? tab[3 * k] : rs::kNoRoot, c1 = have ? tab[3 * k + 1] : rs::kNoRoot, c2 = have ? tab[3 * k + 2] : rs::kNoRoot;
-    for (;;) {
-      const int thr = best > rs::kSample - 1 ? best : rs::kSample - 1;
-      const bool reached = have && (k < niters || k == bk);  // the roots of the iteration being processed are all looked at
-      const bool nosample = reached && c0 == rs::kNoSample && 3 * k > done;
-      int r = -1;
-      if (reached && !nosample) {
-        if (c2 > thr && 3 * k + 2 > done) r = 2;
-        if (c1 > thr && 3 * k + 1 > done) r = 1;
-        if (c0 > thr && 3 * k > done) r = 0;
-      }
-      const unsigned long long hit = __ballot(nosample || r >= 0);
-      if (hit == 0ull) break;
-      const int L = __ffsll((long long)hit) - 1;
-      const int rL = __shfl(r, L, 64);
-      const int cL = __shfl(r == 0 ? c0 : (r == 1 ? c1 : c2), L, 64);
-      if (rL < 0) {  // lane L's iteration drew no sample: the loop ends there
-        stop = base + L;
-        break;
-      }
-      best = cL;
-      bk = base + L;
-      br = rL;
-      done = 3 * bk + br;
-      niters = rs::update_num_iters(confidence, (double)(N - cL) / N, niters);
-    }
-  }
-  *best_k = bk;
-  *best_r = br;
-  *iters = stop >= 0 ? stop : (niters > bk + 1 ? niters : bk + 1);
-  return best;
-}
-
 __global__ void __launch_bounds__(256) ransac_select_kernel(const float4* __restrict__ matches, int B, int N, const int* __restrict__ table,
                                                             double confidence, int max_iters, unsigned long long seed, double* __restrict__ Fd,
                                                             float* __restrict__ F_out, int* __restrict__ n_inliers, int* __restrict__ iters_run,
@@ -144,7 +87,7 @@ __global__ void __launch_bounds__(256) ransac_select_kernel(const float4* __rest
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);  // one wavefront per pair
   if (b >= B) return;
   int bk, br, it;
-  const int best = select_wave(table + (size_t)b * max_iters * rs::kMaxRoots, N, confidence, max_iters, &bk, &br, &it);
+  const int best = select_wave<rs::kMaxRoots, rs::kSample>(table + (size_t)b * max_iters * rs::kMaxRoots, N, confidence, max_iters, &bk, &br, &it);
   if ((threadIdx.x & 63) != 0) return;
   double Fw[9];
 #pragma unroll
@@ -152,16 +95,8 @@ __global__ void __launch_bounds__(256) ransac_select_kernel(const float4* __rest
   if (bk >= 0) {
     const float4* mrow = matches + (size_t)b * N;
     auto pts = [&](int i) { return mrow[i]; };
-    int idx[rs::kSample];
-    rs::draw_sample(seed, bk, N, pts, idx);  // succeeded in the count launch: same stream, same sample
-    float x1[rs::kSample], y1[rs::kSample], x2[rs::kSample], y2[rs::kSample];
-#pragma unroll
-    for (int i = 0; i < rs::kSample; ++i) {
-      const float4 m = mrow[idx[i]];
-      x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
-    }
     double F[9 * rs::kMaxRoots];
-    rs::seven_point(x1, y1, x2, y2, F);
+    rs::solve_iteration(seed, bk, N, pts, F);  // gave a sample in the count launch: same stream, same sample, same roots
 #pragma unroll
     for (int r = 0; r < rs::kMaxRoots; ++r)
       if (r == br) {
@@ -179,23 +114,10 @@ __global__ void __launch_bounds__(256) ransac_select_kernel(const float4* __rest
   if (best_hyp != nullptr) { best_hyp[2 * b] = bk; best_hyp[2 * b + 1] = br; }
 }
 
-__global__ void __launch_bounds__(256) ransac_mask_kernel(const float4* __restrict__ matches, int N, const double* __restrict__ Fd,
-                                                          const int* __restrict__ n_inliers, double t2, unsigned char* __restrict__ mask,
-                                                          float4* __restrict__ masked) {
-  const size_t pair = blockIdx.y;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= N) return;
-  double F[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) F[j] = Fd[pair * 9 + j];
-  const float4 m = matches[pair * N + p];
-  const bool in = n_inliers[pair] > 0 && rs::is_inlier(F, m.x, m.y, m.z, m.w, t2);
-  mask[pair * N + p] = in ? 1 : 0;
-  if (masked != nullptr) {
-    const float qn = __builtin_nanf("");
-    masked[pair * N + p] = in ? m : make_float4(qn, qn, qn, qn);
-  }
-}
+struct MaskF {  // mask_kernel's Model
+  double t2;
+  __device__ bool is_inlier(const double* F, size_t, const float4& m) const { return rs::is_inlier(F, m.x, m.y, m.z, m.w, t2); }
+};
 
 // The fp64 route of cheirality_pair (cheirality_body.h) for one correspondence and the rotation candidate RR: the same rows, the
 // same normal matrix, the same eigenvector routines and depth tests, so that a correspondence is counted here exactly when the
@@ -271,15 +193,11 @@ __global__ void __launch_bounds__(64) ransac_in_front_kernel(const float* __rest
   mask[pair * N + p] = in ? 1 : 0;
 }
 
-int launched() { return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" size_t dfepe_ransac_workspace_bytes(int B, int N, int max_iters) {
   (void)N;
-  if (B <= 0 || max_iters <= 0) return 0;
-  return (size_t)B * 9 * sizeof(double) + (size_t)B * max_iters * rs::kMaxRoots * sizeof(int);
+  return robust_workspace_bytes(B, max_iters, rs::kMaxRoots, sizeof(int));
 }
 
 extern "C" int dfepe_ransac_fundamental(const float* matches, int B, int N, double threshold, double confidence, int max_iters,
@@ -288,7 +206,7 @@ extern "C" int dfepe_ransac_fundamental(const float* matches, int B, int N, doub
                                         void* stream) {
   if (B < 0 || max_iters <= 0 || !(threshold >= 0.0) || !(confidence >= 0.0 && confidence <= 1.0)) return DFEPE_ERR_INVALID_ARG;
   if (B == 0) return DFEPE_OK;
-  if (N < kMinN || N > kMaxN || B > kMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (N < kMinN || N > kMaxN || B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   if (!matches || !workspace || !F_out || !inlier_mask || !n_inliers || !iters_run) return DFEPE_ERR_INVALID_ARG;
   if (!aligned16(matches) || !aligned16(workspace) || (masked_matches && !aligned16(masked_matches))) return DFEPE_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -297,14 +215,12 @@ extern "C" int dfepe_ransac_fundamental(const float* matches, int B, int N, doub
   int* table = hyp_counts ? hyp_counts : reinterpret_cast<int*>(Fd + (size_t)B * 9);
   const float4* m4 = reinterpret_cast<const float4*>(matches);
   const size_t lds = (size_t)N * sizeof(float4) + (size_t)kHyps * 9 * sizeof(double) + (size_t)(kHyps + kChunk) * sizeof(int);
-  if (lds > 65536 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(ransac_count_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return DFEPE_ERR_HIP;
+  if (!opt_in_lds(ransac_count_kernel, lds)) return DFEPE_ERR_HIP;
   hipLaunchKernelGGL(ransac_count_kernel, dim3((max_iters + kChunk - 1) / kChunk, B), dim3(256), lds, s, m4, N, max_iters, t2,
                      seed, table);
   hipLaunchKernelGGL(ransac_select_kernel, dim3((B + 3) / 4), dim3(256), 0, s, m4, B, N, table, confidence, max_iters, seed, Fd,
                      F_out, n_inliers, iters_run, best_hyp);
-  hipLaunchKernelGGL(ransac_mask_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, m4, N, Fd, n_inliers, t2, inlier_mask,
+  hipLaunchKernelGGL(mask_kernel<MaskF>, dim3((N + 255) / 256, B), dim3(256), 0, s, m4, N, Fd, n_inliers, MaskF{t2}, inlier_mask,
                      reinterpret_cast<float4*>(masked_matches));
   return launched();
 }
@@ -314,7 +230,7 @@ extern "C" int dfepe_ransac_in_front(const float* E, const float* K, const float
   if (B < 0 || N < 0) return DFEPE_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return DFEPE_OK;
   if (!E || !K || !matches || !winner || !mask || !aligned16(matches)) return DFEPE_ERR_INVALID_ARG;
-  if (B > kMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(ransac_in_front_kernel, dim3((N + 63) / 64, B), dim3(64), 0, static_cast<hipStream_t>(stream), E, K,
                      reinterpret_cast<const float4*>(matches), N, depth_thres, winner, mask);
   return launched();

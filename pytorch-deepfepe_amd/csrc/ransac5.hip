@@ -14,11 +14,11 @@
 //           the correspondences -- each lane normalises one correspondence once (the divisions) and tests it against every
 //           hypothesis of the chunk (__ballot / __popcll, integer LDS atomics: order-free) -- and the counts go to the
 //           [B, max_iters, 10] table, the hypotheses optionally to hyp_E.
-//   select  one wavefront per pair: the sequential rule over the table, then the winning sample drawn and solved again by the same
-//           device functions (bit for bit the hypothesis the count launch scored).
-//   mask    one lane per correspondence: the winner's inlier mask and the NaN-masked copy of the matches.
-#include "dfepe_common.h"
+//   select  one wavefront per pair: the sequential rule over the table (select_wave, robust_dev.h), then the winning iteration
+//           solved again by r5::solve_iteration (bit for bit the hypothesis the count launch scored).
+//   mask    robust_dev.h's mask_kernel around r5::is_inlier on normalised coordinates.
 #include "ransac5_math.h"
+#include "robust_dev.h"
 
 namespace {
 
@@ -26,29 +26,7 @@ constexpr int kChunk5 = 16;                          // iterations per workgroup
 constexpr int kHyps5 = kChunk5 * r5::kMaxRoots;      // hypotheses per workgroup
 constexpr int kMaxN5 = 4096;                         // correspondences staged in LDS (16 B each)
 constexpr int kMinN5 = 6;                            // with 5 OpenCV returns the stacked models of the one sample (not built)
-constexpr int kMaxPairs5 = 65535;                    // pairs go on the grid's y dimension
 constexpr int kSelectWaves = 4;                      // pairs per workgroup of the select launch
-
-// A lane's view of a workspace whose element i of lane l is at [i * S + l].
-template <int S>
-struct LaneWork {
-  double* p;
-  __device__ double& operator[](int i) const { return p[i * S]; }
-};
-
-// The sample of iteration k in normalised coordinates, solved: the solutions are left in w[r5::kOffE ..].
-template <class W, class P>
-__device__ inline int solve_iteration(W& w, const P& pts, const r5::Cam& cam, unsigned long long seed, int k, int N) {
-  int idx[r5::kSample];
-  r5::draw_sample(seed, k, N, idx);
-  double x1[r5::kSample], y1[r5::kSample], x2[r5::kSample], y2[r5::kSample];
-#pragma unroll
-  for (int i = 0; i < r5::kSample; ++i) {
-    const float4 m = pts(idx[i]);
-    x1[i] = r5::norm_x(cam, m.x); y1[i] = r5::norm_y(cam, m.y); x2[i] = r5::norm_x(cam, m.z); y2[i] = r5::norm_y(cam, m.w);
-  }
-  return r5::five_point(w, x1, y1, x2, y2);
-}
 
 __global__ void __launch_bounds__(256) ransac5_count_kernel(const float4* __restrict__ matches, const float* __restrict__ K, int N,
                                                             int max_iters, double threshold, unsigned long long seed,
@@ -70,9 +48,9 @@ __global__ void __launch_bounds__(256) ransac5_count_kernel(const float4* __rest
     const int k = k0 + tid;
     int n = 0;
     if (k < max_iters) {
-      LaneWork<kChunk5> w{work + tid};
+      r5::LaneWork<kChunk5> w{work + tid};
       auto pts = [&](int i) { return lds_pts5[i]; };
-      n = solve_iteration(w, pts, cam, seed, k, N);
+      n = r5::solve_iteration(w, pts, cam, seed, k, N);
     }
     nroots[tid] = n;
   }
@@ -111,46 +89,6 @@ __global__ void __launch_bounds__(256) ransac5_count_kernel(const float4* __rest
   }
 }
 
-// r5::select_best (the sequential definition) with one wavefront per pair, as select_wave of ransac.hip: the table is read 64
-// iterations at a time, one lane per iteration with its ten counts, and the next model the sequential loop would take -- the first
-// entry, in (k, root) order, past the last one taken, of an iteration the loop still reaches, whose count beats max(best, 4) -- is
-// found by a ballot.
-__device__ inline int select_wave5(const int* __restrict__ tab, int N, double confidence, int max_iters, int* best_k, int* best_r,
-                                   int* iters) {
-  const int lane = threadIdx.x & 63;
-  int best = 0, niters = max_iters, bk = -1, br = -1, done = -1;  // done: last entry (10 k + r) taken
-  for (int base = 0; base < max_iters; base += 64) {
-    if (base >= niters) break;  // no iteration from here on is reached (bk < base)
-    const int k = base + lane;
-    const bool have = k < max_iters;
-    int c[r5::kMaxRoots];
-#pragma unroll
-    for (int r = 0; r < r5::kMaxRoots; ++r) c[r] = have ? tab[r5::kMaxRoots * k + r] : r5::kNoRoot;
-    for (;;) {
-      const int thr = best > r5::kSample - 1 ? best : r5::kSample - 1;
-      const bool reached = have && (k < niters || k == bk);  // the roots of the iteration being processed are all looked at
-      int r = -1, cr = 0;
-      if (reached) {
-#pragma unroll
-        for (int q = r5::kMaxRoots - 1; q >= 0; --q)
-          if (c[q] > thr && r5::kMaxRoots * k + q > done) { r = q; cr = c[q]; }
-      }
-      const unsigned long long hit = __ballot(r >= 0);
-      if (hit == 0ull) break;
-      const int L = __ffsll((long long)hit) - 1;
-      br = __shfl(r, L, 64);
-      best = __shfl(cr, L, 64);
-      bk = base + L;
-      done = r5::kMaxRoots * bk + br;
-      niters = r5::update_num_iters(confidence, (double)(N - best) / N, niters);
-    }
-  }
-  *best_k = bk;
-  *best_r = br;
-  *iters = niters > bk + 1 ? niters : bk + 1;
-  return best;
-}
-
 __global__ void __launch_bounds__(64 * kSelectWaves) ransac5_select_kernel(
     const float4* __restrict__ matches, const float* __restrict__ K, int B, int N, const int* __restrict__ table, double confidence,
     int max_iters, unsigned long long seed, double* __restrict__ Ed, float* __restrict__ E_out, int* __restrict__ n_inliers,
@@ -160,7 +98,7 @@ __global__ void __launch_bounds__(64 * kSelectWaves) ransac5_select_kernel(
   const int b = blockIdx.x * kSelectWaves + wave;  // one wavefront per pair
   if (b >= B) return;
   int bk, br, it;
-  const int best = select_wave5(table + (size_t)b * max_iters * r5::kMaxRoots, N, confidence, max_iters, &bk, &br, &it);
+  const int best = select_wave<r5::kMaxRoots, r5::kSample>(table + (size_t)b * max_iters * r5::kMaxRoots, N, confidence, max_iters, &bk, &br, &it);
   if ((threadIdx.x & 63) != 0) return;
   double Ew[9];
 #pragma unroll
@@ -168,8 +106,8 @@ __global__ void __launch_bounds__(64 * kSelectWaves) ransac5_select_kernel(
   if (bk >= 0) {
     const float4* mrow = matches + (size_t)b * N;
     auto pts = [&](int i) { return mrow[i]; };
-    LaneWork<1> w{work[wave]};
-    solve_iteration(w, pts, r5::cam_of(K + (size_t)b * 9), seed, bk, N);  // same stream, same sample, same solutions
+    r5::LaneWork<1> w{work[wave]};
+    r5::solve_iteration(w, pts, r5::cam_of(K + (size_t)b * 9), seed, bk, N);  // same stream, same sample, same solutions
 #pragma unroll
     for (int j = 0; j < 9; ++j) Ew[j] = w[r5::kOffE + 9 * br + j];
   }
@@ -183,35 +121,21 @@ __global__ void __launch_bounds__(64 * kSelectWaves) ransac5_select_kernel(
   if (best_hyp != nullptr) { best_hyp[2 * b] = bk; best_hyp[2 * b + 1] = br; }
 }
 
-__global__ void __launch_bounds__(256) ransac5_mask_kernel(const float4* __restrict__ matches, const float* __restrict__ K, int N,
-                                                           const double* __restrict__ Ed, const int* __restrict__ n_inliers,
-                                                           double threshold, unsigned char* __restrict__ mask,
-                                                           float4* __restrict__ masked) {
-  const size_t pair = blockIdx.y;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= N) return;
-  double E[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) E[j] = Ed[pair * 9 + j];
-  const r5::Cam cam = r5::cam_of(K + pair * 9);
-  const float4 m = matches[pair * N + p];
-  const bool in = n_inliers[pair] > 0 && r5::is_inlier(E, r5::norm_x(cam, m.x), r5::norm_y(cam, m.y), r5::norm_x(cam, m.z),
-                                                       r5::norm_y(cam, m.w), r5::threshold2(cam, threshold));
-  mask[pair * N + p] = in ? 1 : 0;
-  if (masked != nullptr) {
-    const float qn = __builtin_nanf("");
-    masked[pair * N + p] = in ? m : make_float4(qn, qn, qn, qn);
+struct MaskE {  // mask_kernel's Model
+  const float* K;
+  double threshold;
+  __device__ bool is_inlier(const double* E, size_t pair, const float4& m) const {
+    const r5::Cam cam = r5::cam_of(K + pair * 9);
+    return r5::is_inlier(E, r5::norm_x(cam, m.x), r5::norm_y(cam, m.y), r5::norm_x(cam, m.z), r5::norm_y(cam, m.w),
+                         r5::threshold2(cam, threshold));
   }
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+};
 
 }  // namespace
 
 extern "C" size_t dfepe_ransac5_workspace_bytes(int B, int N, int max_iters) {
   (void)N;
-  if (B <= 0 || max_iters <= 0) return 0;
-  return (size_t)B * 9 * sizeof(double) + (size_t)B * max_iters * r5::kMaxRoots * sizeof(int);
+  return robust_workspace_bytes(B, max_iters, r5::kMaxRoots, sizeof(int));
 }
 
 extern "C" int dfepe_ransac_essential(const float* matches, const float* K, int B, int N, double threshold, double confidence,
@@ -220,7 +144,7 @@ extern "C" int dfepe_ransac_essential(const float* matches, const float* K, int 
                                       double* hyp_E, float* masked_matches, void* stream) {
   if (B < 0 || max_iters <= 0 || !(threshold >= 0.0) || !(confidence >= 0.0 && confidence <= 1.0)) return DFEPE_ERR_INVALID_ARG;
   if (B == 0) return DFEPE_OK;
-  if (N < kMinN5 || N > kMaxN5 || B > kMaxPairs5) return DFEPE_ERR_UNSUPPORTED;
+  if (N < kMinN5 || N > kMaxN5 || B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   if (!matches || !K || !workspace || !E_out || !inlier_mask || !n_inliers || !iters_run) return DFEPE_ERR_INVALID_ARG;
   if (!aligned16(matches) || !aligned16(workspace) || (masked_matches && !aligned16(masked_matches))) return DFEPE_ERR_INVALID_ARG;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -229,14 +153,12 @@ extern "C" int dfepe_ransac_essential(const float* matches, const float* K, int 
   const float4* m4 = reinterpret_cast<const float4*>(matches);
   // 16 N + 38592 bytes: above 64 KiB (the attribute below) from N = 1685
   const size_t lds = (size_t)N * sizeof(float4) + (size_t)r5::kWork * kChunk5 * sizeof(double) + (size_t)(kHyps5 + kChunk5) * sizeof(int);
-  if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void*>(ransac5_count_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return DFEPE_ERR_HIP;
+  if (!opt_in_lds(ransac5_count_kernel, lds)) return DFEPE_ERR_HIP;
   hipLaunchKernelGGL(ransac5_count_kernel, dim3((max_iters + kChunk5 - 1) / kChunk5, B), dim3(256), lds, s, m4, K, N, max_iters,
                      threshold, seed, table, hyp_E);
   hipLaunchKernelGGL(ransac5_select_kernel, dim3((B + kSelectWaves - 1) / kSelectWaves), dim3(64 * kSelectWaves), 0, s, m4, K, B, N,
                      table, confidence, max_iters, seed, Ed, E_out, n_inliers, iters_run, best_hyp);
-  hipLaunchKernelGGL(ransac5_mask_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, m4, K, N, Ed, n_inliers, threshold, inlier_mask,
-                     reinterpret_cast<float4*>(masked_matches));
-  return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
+  hipLaunchKernelGGL(mask_kernel<MaskE>, dim3((N + 255) / 256, B), dim3(256), 0, s, m4, N, Ed, n_inliers, MaskE{K, threshold},
+                     inlier_mask, reinterpret_cast<float4*>(masked_matches));
+  return launched();
 }

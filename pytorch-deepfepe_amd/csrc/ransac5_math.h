@@ -439,37 +439,35 @@ RS_HD bool is_inlier(const double* E, double x1, double y1, double x2, double y2
   return r * r <= t2 * (a * a + b * b + a2 * a2 + b2 * b2);
 }
 
-// OpenCV's RANSACUpdateNumIters(p, ep, 5, niters); (1 - ep)^5 by multiplications so that every build forms the same value.
-RS_HD int update_num_iters(double p, double ep, int niters) {
-  p = fmin(fmax(p, 0.0), 1.0);
-  ep = fmin(fmax(ep, 0.0), 1.0);
-  const double num = fmax(1.0 - p, DBL_MIN);
-  const double q = 1.0 - ep, q2 = q * q, q4 = q2 * q2;
-  const double den = 1.0 - q4 * q;
-  if (den < DBL_MIN) return 0;
-  const double ln = log(num), ld = log(den);
-  return (ld >= 0.0 || -ln >= niters * (-ld)) ? niters : (int)rint(ln / ld);
+// A view of a workspace whose element i is at p[i * S]: S lanes side by side in LDS, each with every S-th double (S = 1: a
+// plain array).
+template <int S>
+struct LaneWork {
+  double* p;
+  RS_HD double& operator[](int i) const { return p[i * S]; }
+};
+
+// Iteration k of a pair, whole: its sample drawn, gathered into normalised coordinates and solved; the solutions are left in
+// w[kOffE ..].  Every launch that needs iteration k's models (ransac5.hip, lmeds.hip: count / median and select) goes through
+// here, which is what makes the winner come out again bit for bit.  P as in rs::draw_sample.  Returns the number of solutions.
+template <class W, class P>
+RS_HD int solve_iteration(W& w, const P& pts, const Cam& cam, uint64_t seed, int k, int N) {
+  int idx[kSample];
+  draw_sample(seed, k, N, idx);
+  double x1[kSample], y1[kSample], x2[kSample], y2[kSample];
+#pragma unroll
+  for (int i = 0; i < kSample; ++i) {
+    const auto m = pts(idx[i]);
+    x1[i] = norm_x(cam, m.x); y1[i] = norm_y(cam, m.y); x2[i] = norm_x(cam, m.z); y2[i] = norm_y(cam, m.w);
+  }
+  return five_point(w, x1, y1, x2, y2);
 }
 
-// The sequential selection rule over one pair's count table counts[k * 10 + r] (k < max_iters): rs::select_best with ten slots,
-// the floor max(best, 4) and no iteration without a sample.  This is the definition; select_wave5 (csrc/ransac5.hip) evaluates
-// the same rule a wavefront at a time.
+// The iteration bound and the sequential selection rule are ransac_math.h's, with 5 points and 10 slots; this table never holds
+// rs::kNoSample (five distinct indices always exist), so that rule's stop is never taken here.
+RS_HD int update_num_iters(double p, double ep, int niters) { return rs::update_num_iters<kSample>(p, ep, niters); }
 RS_HD int select_best(const int* counts, int N, double confidence, int max_iters, int* best_k, int* best_r, int* iters) {
-  int best = 0, niters = max_iters, k = 0;
-  *best_k = -1;
-  *best_r = -1;
-  for (; k < niters; ++k)
-    for (int r = 0; r < kMaxRoots; ++r) {
-      const int c = counts[kMaxRoots * k + r];
-      if (c > (best > kSample - 1 ? best : kSample - 1)) {
-        best = c;
-        *best_k = k;
-        *best_r = r;
-        niters = update_num_iters(confidence, (double)(N - c) / N, niters);
-      }
-    }
-  *iters = k;
-  return best;
+  return rs::select_best<kMaxRoots, kSample>(counts, N, confidence, max_iters, best_k, best_r, iters);
 }
 
 }  // namespace r5

@@ -19,6 +19,9 @@ constexpr int kSample = 7;          // points per minimal sample (7-point solver
 constexpr int kMaxAttempts = 1000;  // draws of a sample before an iteration gives up (OpenCV's maxAttempts)
 constexpr int kMaxRoots = 3;
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+// Count-table codes (dfepe_ransac_fundamental's hyp_counts): a root that does not exist, an iteration that drew no sample.
+constexpr int kNoRoot = -1;
+constexpr int kNoSample = -2;
 
 RS_HD uint64_t splitmix64(uint64_t x) {
   x += kGolden;
@@ -268,6 +271,21 @@ RS_HD int seven_point(const float* px1, const float* py1, const float* px2, cons
   return n;
 }
 
+// Iteration k of a pair, whole: its sample drawn, gathered and solved.  The count (median) launch and the select launch both go
+// through here, which is what makes the winner come out again bit for bit.  Returns the number of roots, or kNoSample.
+template <class P>
+RS_HD int solve_iteration(uint64_t seed, int k, int N, const P& pts, double* F) {
+  int idx[kSample];
+  if (!draw_sample(seed, k, N, pts, idx)) return kNoSample;
+  float x1[kSample], y1[kSample], x2[kSample], y2[kSample];
+#pragma unroll
+  for (int i = 0; i < kSample; ++i) {
+    const auto m = pts(idx[i]);
+    x1[i] = m.x; y1[i] = m.y; x2[i] = m.z; y2[i] = m.w;
+  }
+  return seven_point(x1, y1, x2, y2, F);
+}
+
 // OpenCV's FMEstimatorCallback::computeError decision without the divisions: err = max(d1^2, d2^2) <= t2, with d2 the distance of
 // x2 to the line F x1 and d1 the distance of x1 to the line F^T x2 (both share the residual r = x2^T F x1).
 RS_HD bool is_inlier(const double* F, double x1, double y1, double x2, double y2, double t2) {
@@ -278,43 +296,53 @@ RS_HD bool is_inlier(const double* F, double x1, double y1, double x2, double y2
   return rr <= t2 * (a * a + b * b) && rr <= t2 * (a2 * a2 + b2 * b2);
 }
 
-// OpenCV's RANSACUpdateNumIters(p, ep, 7, niters); (1 - ep)^7 by multiplications so that every build forms the same value.
+// OpenCV's RANSACUpdateNumIters(p, ep, M, niters) for the three model sizes built (7-point F, five-point E, 4-point H);
+// (1 - ep)^M by multiplications, each M in its own fixed order, so that every build forms the same value.
+template <int M>
 RS_HD int update_num_iters(double p, double ep, int niters) {
+  static_assert(M == 7 || M == 5 || M == 4, "model sizes of the estimators built");
   p = fmin(fmax(p, 0.0), 1.0);
   ep = fmin(fmax(ep, 0.0), 1.0);
   const double num = fmax(1.0 - p, DBL_MIN);
   const double q = 1.0 - ep, q2 = q * q, q4 = q2 * q2;
-  const double den = 1.0 - q4 * q2 * q;
+  double den;
+  if constexpr (M == 7) den = 1.0 - q4 * q2 * q;
+  else if constexpr (M == 5) den = 1.0 - q4 * q;
+  else den = 1.0 - q2 * q2;
   if (den < DBL_MIN) return 0;
   const double ln = log(num), ld = log(den);
   return (ld >= 0.0 || -ln >= niters * (-ld)) ? niters : (int)rint(ln / ld);
 }
 
-// Count-table codes (dfepe_ransac_fundamental's hyp_counts): a root that does not exist, an iteration that drew no sample.
-constexpr int kNoRoot = -1;
-constexpr int kNoSample = -2;
-
-// The sequential selection rule over one pair's count table counts[k * 3 + r] (k < max_iters).  Writes the winning (k, r) or
-// (-1, -1) and returns the best count (0 when no model); *iters = iterations consumed (the k the loop stopped at).  This is the
-// definition: the select launch evaluates the same rule a wavefront at a time (select_wave, csrc/ransac.hip).
+// The sequential selection rule of all three RANSAC estimators over one pair's count table counts[k * ROOTS + r] (k < max_iters;
+// ROOTS slots an iteration, SAMPLE points a model: <3, 7> F, <10, 5> E, <1, 4> H).  Writes the winning (k, r) or (-1, -1) and
+// returns the best count (0 when no model); *iters = iterations consumed (the k the loop stopped at).  This is the definition:
+// the select launches evaluate the same rule a wavefront at a time (select_wave, csrc/robust_dev.h).
+template <int ROOTS, int SAMPLE>
 RS_HD int select_best(const int* counts, int N, double confidence, int max_iters, int* best_k, int* best_r, int* iters) {
   int best = 0, niters = max_iters, k = 0;
   *best_k = -1;
   *best_r = -1;
   for (; k < niters; ++k) {
-    if (counts[3 * k] == kNoSample) break;  // as OpenCV: the loop ends (and no model exists when k == 0)
-    for (int r = 0; r < kMaxRoots; ++r) {
-      const int c = counts[3 * k + r];
-      if (c > (best > kSample - 1 ? best : kSample - 1)) {
+    if (counts[ROOTS * k] == kNoSample) break;  // as OpenCV: the loop ends (and no model exists when k == 0)
+    for (int r = 0; r < ROOTS; ++r) {
+      const int c = counts[ROOTS * k + r];
+      if (c > (best > SAMPLE - 1 ? best : SAMPLE - 1)) {
         best = c;
         *best_k = k;
         *best_r = r;
-        niters = update_num_iters(confidence, (double)(N - c) / N, niters);
+        niters = update_num_iters<SAMPLE>(confidence, (double)(N - c) / N, niters);
       }
     }
   }
   *iters = k;
   return best;
+}
+
+// The 7-point estimator's instantiations under the names its callers and the host emulation use.
+RS_HD int update_num_iters(double p, double ep, int niters) { return update_num_iters<kSample>(p, ep, niters); }
+RS_HD int select_best(const int* counts, int N, double confidence, int max_iters, int* best_k, int* best_r, int* iters) {
+  return select_best<kMaxRoots, kSample>(counts, N, confidence, max_iters, best_k, best_r, iters);
 }
 
 }  // namespace rs

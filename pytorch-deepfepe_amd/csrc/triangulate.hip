@@ -12,7 +12,6 @@
 namespace {
 
 constexpr int kTriBlock = 64;
-constexpr int kTriMaxPairs = 65535;  // pairs go on the grid's y dimension
 
 __global__ void __launch_bounds__(kTriBlock) triangulate_kernel(const float* __restrict__ P1, int p1_stride, const float* __restrict__ P2,
                                                                 int p2_stride, const float4* __restrict__ matches, int N,
@@ -75,8 +74,6 @@ __global__ void __launch_bounds__(kTriBlock) reproject_kernel(const float* __res
   if (inside != nullptr) inside[i] = tri::within(xf, yf, image_w, image_h) ? 1 : 0;
 }
 
-int launched() { return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP; }
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 bool stride_ok(int s, int row) { return s == 0 || s == row; }
 
 }  // namespace
@@ -86,7 +83,7 @@ extern "C" int dfepe_triangulate(const float* P1, int p1_stride, const float* P2
   if (B < 0 || N < 0 || !stride_ok(p1_stride, 12) || !stride_ok(p2_stride, 12)) return DFEPE_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return DFEPE_OK;
   if (!P1 || !P2 || !matches || !Xh || !aligned16(matches) || !aligned16(Xh)) return DFEPE_ERR_INVALID_ARG;
-  if (B > kTriMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(triangulate_kernel, dim3((N + kTriBlock - 1) / kTriBlock, B), dim3(kTriBlock), 0, static_cast<hipStream_t>(stream), P1,
                      p1_stride, P2, p2_stride, reinterpret_cast<const float4*>(matches), N, reinterpret_cast<float4*>(Xh));
   return launched();
@@ -97,7 +94,7 @@ extern "C" int dfepe_two_view_structure(const float* Rt, unsigned flags, const f
   if (B < 0 || N < 0 || (flags & ~DFEPE_POSE_CAMERA_MOTION) != 0u) return DFEPE_ERR_INVALID_ARG;
   if (B == 0 || N == 0) return DFEPE_OK;
   if (!Rt || !K || !matches || !aligned16(matches) || (!X && !z1 && !z2)) return DFEPE_ERR_INVALID_ARG;
-  if (B > kTriMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(two_view_structure_kernel, dim3((N + kTriBlock - 1) / kTriBlock, B), dim3(kTriBlock), 0, static_cast<hipStream_t>(stream),
                      Rt, flags, K, reinterpret_cast<const float4*>(matches), N, winner, scale, clamp, X, z1, z2);
   return launched();
@@ -109,7 +106,7 @@ extern "C" int dfepe_reproject(const float* X, const float* Rt, int rt_stride, u
     return DFEPE_ERR_INVALID_ARG;
   if (B == 0 || M == 0) return DFEPE_OK;
   if (!X || !Rt || !K || !x) return DFEPE_ERR_INVALID_ARG;
-  if (B > kTriMaxPairs) return DFEPE_ERR_UNSUPPORTED;
+  if (B > kMaxGridY) return DFEPE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(reproject_kernel, dim3((M + kTriBlock - 1) / kTriBlock, B), dim3(kTriBlock), 0, static_cast<hipStream_t>(stream), X, Rt,
                      rt_stride, flags, K, k_stride, M, image_w, image_h, x, z, inside);
   return launched();

@@ -61,12 +61,6 @@ struct Writer {
   void put(const T* v, size_t n = 1) { fwrite(v, sizeof(T), n, f); }
 };
 
-bool solve_idx(const P4* p, const int* idx, double* H) {
-  float x1[4], y1[4], x2[4], y2[4];
-  for (int i = 0; i < 4; ++i) { x1[i] = p[idx[i]].x; y1[i] = p[idx[i]].y; x2[i] = p[idx[i]].z; y2[i] = p[idx[i]].w; }
-  return hg::solve4(x1, y1, x2, y2, H);
-}
-
 void do_pair(Reader& in, Writer& out) {
   int n, max_iters;
   double threshold, confidence;
@@ -84,10 +78,10 @@ void do_pair(Reader& in, Writer& out) {
   auto at = [&](int i) { return p[i]; };
   if (sampled) {
     for (int k = 0; k < max_iters; ++k) {
-      int idx[4];
-      if (!hg::draw_sample4(seed, k, n, at, idx)) continue;
       double H[9];
-      if (!solve_idx(p, idx, H)) { table[k] = rs::kNoRoot; continue; }
+      const int st = hg::solve_iteration(seed, k, n, at, H);
+      if (st == rs::kNoSample) continue;
+      if (st == 0) { table[k] = rs::kNoRoot; continue; }
       int c = 0;
       for (int i = 0; i < n; ++i) c += hg::is_inlier(H, p[i].x, p[i].y, p[i].z, p[i].w, t2) ? 1 : 0;
       table[k] = c;
@@ -97,10 +91,9 @@ void do_pair(Reader& in, Writer& out) {
   double Hm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (sampled) best = hg::select_best(table.data(), n, confidence, max_iters, &bk, &iters);
   if (n == 4 || (sampled && bk >= 0)) {
-    int idx[4] = {0, 1, 2, 3};
-    if (sampled) hg::draw_sample4(seed, bk, n, at, idx);
+    const int all4[4] = {0, 1, 2, 3};
     double H[9];
-    const bool ok = solve_idx(p, idx, H);
+    const bool ok = sampled ? hg::solve_iteration(seed, bk, n, at, H) == 1 : hg::solve_sample(at, all4, H);
     if (ok) memcpy(Hm, H, sizeof(H));
     if (!sampled) best = ok ? 4 : 0;
   } else if (n > 4 && all) {
@@ -170,8 +163,9 @@ int main(int argc, char** argv) {
       P4 p[4];
       in.get(p, 4);
       const int idx[4] = {0, 1, 2, 3};
+      auto at = [&](int i) { return p[i]; };
       double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      const int ok = solve_idx(p, idx, H) ? 1 : 0;
+      const int ok = hg::solve_sample(at, idx, H) ? 1 : 0;
       out.put(&ok); out.put(H, 9);
     } else if (op == 3) {
       int n, max_iters;

@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import homography_cases as hc  # noqa: E402
 import homography_ref as hr  # noqa: E402
+import rule_tables  # noqa: E402
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EMU_DIR = os.path.join(REPO, "tests", "emu")
@@ -223,6 +224,17 @@ def test_host_build_small_records(emu, tmp_path):
         assert struct.unpack_from("<i", buf, off)[0] == hr.update_num_iters4(p, ep, ni), (p, ep, ni)
         off += 4
     assert off == len(buf)
+
+
+def test_shared_rule_as_1_slot_of_4_points_on_the_edge_tables(emu, tmp_path):
+    """rs::select_best<1, 4> on tests/rule_tables.py: no sample at k = 0 and past the first model, ties, confidence 0 and 1 --
+    the three outputs it has with one slot against this estimator's own restatement."""
+    cases = [(tab[:, 0].copy(), N, conf) for tab, N, conf in rule_tables.tables(1, hr.NO_SAMPLE)]
+    payload = b"".join(struct.pack("<iidi", 3, N, conf, len(tab)) + tab.astype("<i4").tobytes() for tab, N, conf in cases)
+    buf = run_emu(emu, payload, tmp_path, "rule")
+    assert len(buf) == 12 * len(cases)
+    for i, (tab, N, conf) in enumerate(cases):
+        assert struct.unpack_from("<3i", buf, 12 * i) == hr.select(tab, N, conf, len(tab)), (tab.tolist(), N, conf)
 
 
 def test_host_build_is_clean_under_the_sanitizers(emu, tmp_path):

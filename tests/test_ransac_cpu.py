@@ -12,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ransac_ref as ref  # noqa: E402
+import rule_tables  # noqa: E402
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EMU_DIR = os.path.join(REPO, "tests", "emu")
@@ -197,6 +198,17 @@ def test_selection_rule_agrees_on_synthetic_tables(emu):
         tab = np.ascontiguousarray(tab, dtype=np.int32)
         emu.emu_ransac_select(_p(tab), N, conf, T, _p(out))
         assert tuple(out) == ref.select(tab, N, conf, T), trial
+
+
+def test_shared_rule_as_3_roots_of_7_points_on_the_edge_tables(emu):
+    """rs::select_best<3, 7> on tests/rule_tables.py: several improving roots in one iteration, no sample at k = 0 and past the
+    first model, ties, confidence 0 and 1 -- all four outputs against this estimator's own restatement."""
+    tab, N, conf = rule_tables.climbing(3)
+    assert ref.select(tab, N, conf, len(tab)) == (99, 5, 2, 6)  # every root of k = 5 was looked at, k = 6 was not
+    for tab, N, conf in rule_tables.tables(3, ref.NO_SAMPLE):
+        out = np.zeros(4, np.int32)
+        emu.emu_ransac_select(_p(tab), N, conf, len(tab), _p(out))
+        assert tuple(out) == ref.select(tab, N, conf, len(tab)), (tab.tolist(), N, conf)
 
 
 def test_inlier_decision_matches_the_error_outside_the_band(emu):
