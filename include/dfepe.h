@@ -1059,6 +1059,66 @@ int dfepe_homography_transfer(const double *H, const float *matches, const int *
 int dfepe_homography_corners(const double *H_est, const double *H_gt, int B, int height, int width, const double *thresh, int T,
                              double *mean_dist, unsigned char *correct, void *stream);
 
+/*
+ * The rest of the reference's front-end table (deepFEPE/evaluate_frontend.py:45: correctness, repeatability, localization_err,
+ * mscore, mAP; correctness is dfepe_homography_corners), batched over B image pairs.  All arithmetic and all floating-point
+ * arguments are fp64.  No atomics; every output cell has one writer and every sum a fixed order, so two calls on the same input
+ * are bit-identical; no host synchronisation, no allocation; all refusals are made before anything is launched, in the order
+ * in which they are listed.
+ *
+ * dfepe_keypoint_repeatability: compute_repeatability (evaluations/detector_evaluation.py:150-279).
+ *   kp1 [B,N1,C], kp2 [B,N2,C]: rows (x, y[, prob]) of image 1 (data['prob']) and image 2 (data['warped_prob']); C is 2 or 3
+ *   n1, n2 [B] int32 or NULL: pair b uses its first clamp(n[b], 0, N) rows; NULL means all.  H [B,9], image 1 to image 2
+ *   height, width >= 1: data['image'].shape.  keep_k >= 0: keep_k_points.  thresh [T] in device memory, T >= 0 (T == 0: only
+ *   kept1, kept2 and n_unwarped are written; the other outputs may then be NULL)
+ *   workspace: dfepe_keypoint_repeatability_workspace_bytes(B, N1, N2) bytes of device memory, 16-byte aligned, overwritten
+ *   repeatability, loc_err [B,T] fp64; count1, count2 [B,T] int32; kept1, kept2, n_unwarped [B] int32
+ *   Refused: B, N1, N2, T or keep_k < 0, C not 2 or 3, height or width < 1: INVALID_ARG.  Then B == 0 returns OK.  N1 or N2 >
+ *   4096, or B > 65535: UNSUPPORTED.  A null kp1 with N1 > 0 (kp2, N2 alike), a null H, kept1, kept2 or n_unwarped; with T > 0 a
+ *   null thresh or [B,T] output; with N1 + N2 > 0 a null or misaligned workspace: INVALID_ARG.
+ *   The definition:
+ *   1 Image-2 points are warped by adj(H) (transposed cofactors: the same projective map as inv(H), no division by the
+ *     determinant) and kept when the warp lies in 0 <= x < width, 0 <= y < height (keep_true_keypoints); the kept points keep
+ *     their own coordinates.  n_unwarped counts the image-2 points whose warp lies in 0 <= x <= width - 1, 0 <= y <= height - 1,
+ *     both ends inclusive, nothing truncated: the warpLabels count of the matching score, stated here because that helper's
+ *     package is not part of the reference's tree.
+ *   2 Image-1 points are warped by H and the warped points kept under the half-open test (filter_keypoints).  A point whose
+ *     homogeneous w is 0 gives what the division gives, and fails both tests through the comparisons themselves.
+ *   3 select_k_best, with C = 3: of each kept set the min(keep_k, n) points that stand last in a stable ascending argsort of the
+ *     probabilities, that is the largest, and among equal probabilities the higher index (numpy's default argsort, which the
+ *     reference calls, is not stable: there the choice among equals at the k-th place is undefined).  NaN sorts above +inf,
+ *     -0 equals +0, as in numpy.  min(keep_k, n) = 0 keeps every point, as numpy's [-0:] does.  With C = 2 nothing is selected.
+ *     kept1, kept2: the sizes N1, N2 after this step.
+ *   4 min1[i]: the Euclidean distance from kept point i of image 1 (warped) to the nearest kept point of image 2, min2 the same
+ *     with the roles swapped.  count1[t] = #{min1 <= thresh[t]} (not strict), 0 when kept2 = 0; count2 alike.
+ *   5 repeatability = (count1 + count2) / (kept1 + kept2); loc_err = sum(counted min1) / (count1 + count2) + sum(counted min2) /
+ *     (count1 + count2); 0 and -1 when nothing is counted.  The reference overwrites its caller's data['prob'][:, :2] with the
+ *     warped points (line 228); nothing here writes to an input.
+ *
+ * dfepe_average_precision: sklearn.metrics.average_precision_score(labels, scores), evaluate_frontend.py:244-275.
+ *   labels [B,M] uint8 (non-zero: positive), scores [B,M]; n_valid [B] int32 or NULL as above.  ap [B]; n_pos [B] int32 or NULL;
+ *   tp_at, cnt_at [B,M] int32 or NULL (each on its own); cells past n_valid get 0.
+ *   Refused: B or M < 0: INVALID_ARG.  B == 0 returns OK.  M > 4096 or B > 65535: UNSUPPORTED.  A null ap, or with M > 0 null
+ *   labels or scores: INVALID_ARG.
+ *   scikit-learn's value groups tied scores; it equals   AP = (1/P) sum over positives i of TP(s_i) / CNT(s_i)   with
+ *   TP(s) = #{j: score_j >= s, label_j = 1} = tp_at, CNT(s) = #{j: score_j >= s} = cnt_at, P = #positives = n_pos: no sort, no
+ *   dependence on the order of equal scores, exact in its integer parts.  ap = 0 for a pair without a valid entry or without a
+ *   positive (evaluate_frontend.py:268-273).  A NaN score is at least as high as nothing: its cnt_at is 0, and the ap of a pair
+ *   with a NaN-scored positive is NaN.
+ *
+ * dfepe_matching_score: evaluate_frontend.py:181.  mscore[b] = 2 n_inliers[b] / (n_kp1[b] + n_unwarped[b]) (all [B] int32, the
+ *   last from dfepe_keypoint_repeatability); a zero denominator gives what the division gives.  B < 0 or (with B > 0) a null
+ *   pointer: INVALID_ARG; B == 0 returns OK.
+ */
+size_t dfepe_keypoint_repeatability_workspace_bytes(int B, int N1, int N2);
+int dfepe_keypoint_repeatability(const double *kp1, const double *kp2, const int *n1, const int *n2, const double *H, int B, int N1,
+                                 int N2, int C, int height, int width, int keep_k, const double *thresh, int T, void *workspace,
+                                 double *repeatability, double *loc_err, int *count1, int *count2, int *kept1, int *kept2,
+                                 int *n_unwarped, void *stream);
+int dfepe_average_precision(const unsigned char *labels, const double *scores, const int *n_valid, int B, int M, double *ap, int *n_pos,
+                            int *tp_at, int *cnt_at, void *stream);
+int dfepe_matching_score(const int *n_inliers, const int *n_kp1, const int *n_unwarped, int B, double *mscore, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

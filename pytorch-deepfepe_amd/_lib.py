@@ -38,6 +38,7 @@ RANSAC5_MIN_N = 6  # dfepe_ransac_essential: with 5 OpenCV returns the stacked m
 HOMOGRAPHY_ALL_POINTS = 1  # dfepe_ransac_homography: cv2's method = 0 (DFEPE_HOMOGRAPHY_ALL_POINTS)
 HOMOGRAPHY_NO_REFINE = 2  # ... no Levenberg-Marquardt step (DFEPE_HOMOGRAPHY_NO_REFINE)
 HOMOGRAPHY_MAX_N = 4096
+DETECTOR_EVAL_MAX_N = 4096  # dfepe_keypoint_repeatability (points per image), dfepe_average_precision (entries per pair): de::kMaxN
 
 _P = c_void_p
 _SIGNATURES = {
@@ -134,6 +135,11 @@ _SIGNATURES = {
     "dfepe_ransac_homography": (c_int, [_P, _P, c_int, c_int, c_double, c_double, c_int, c_ulonglong, c_uint, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_homography_transfer": (c_int, [_P, _P, _P, c_int, c_int, c_double, _P, _P, _P]),
     "dfepe_homography_corners": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
+    "dfepe_keypoint_repeatability_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_keypoint_repeatability": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P, _P,
+                                             _P, _P, _P, _P]),
+    "dfepe_average_precision": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    "dfepe_matching_score": (c_int, [_P, _P, _P, c_int, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

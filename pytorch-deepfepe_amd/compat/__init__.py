@@ -14,6 +14,8 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
                                                                     findHomography in place of cv2.findHomography)
     evaluations.descriptor_evaluation   ->   compat.descriptor_evaluation (compute_homography, homography_estimation; getInliers
                                                                     and getInliers_cv of deepFEPE/evaluate_frontend.py)
+    evaluations.detector_evaluation     ->   compat.detector_evaluation (compute_repeatability, warp_keypoints)
+    deepFEPE.evaluate_frontend          ->   compat.evaluate_frontend (matching score, nn mean AP, the five numbers per pair)
     deepFEPE.dsac_tools.utils_vis       ->   compat.utils_vis       (reproj_and_scatter without the drawing)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)
@@ -25,7 +27,9 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, dsac, eval_tools, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
+from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401
 from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
+from .detector_evaluation import compute_repeatability, compute_repeatability_batch  # noqa: F401
+from .evaluate_frontend import frontend_metrics_batch  # noqa: F401
 from .utils_opencv import findHomography, findHomography_batch  # noqa: F401

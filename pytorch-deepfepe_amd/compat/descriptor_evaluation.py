@@ -6,7 +6,9 @@ estimator ops.ransac_homography, the corner test ops.homography_corners, the inl
 What differs from the reference: 'matches' is an int [M,2] array of (index into keypoints1, index into keypoints2), not a list of
 cv2.DMatch; the random stream of the estimator is this package's (include/dfepe.h), so results agree with cv2's in distribution;
 the reference's print calls are not mirrored; ORB / Hamming matching is not built; homography_estimation takes the loaded
-dicts, not an experiment name (there is no settings.EXPER_PATH here).  Not built: compute_repeatability, the mAP, drawing."""
+dicts, not an experiment name (there is no settings.EXPER_PATH here).  compute_repeatability is in compat/detector_evaluation.py,
+the matching score and the nn mean AP in compat/evaluate_frontend.py.  Not built: the dense-map precision / recall curves
+(compute_tp_fp, compute_pr, compute_loc_error) and drawing."""
 import numpy as np
 import torch
 

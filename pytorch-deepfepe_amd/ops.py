@@ -1684,3 +1684,106 @@ def homography_corners(H_est: Tensor, H_gt: Tensor, height: int, width: int, thr
         rc = _lib.lib().dfepe_homography_corners(_ptr(He), _ptr(Hg), B, int(height), int(width), _ptr(th), T, _ptr(md), _ptr(ok), _stream())
     _lib.check(rc, "dfepe_homography_corners")
     return md, ok
+
+
+# ------------------------------------------------------------------------------------------------
+# front-end detector evaluation: repeatability, localization error, matching score, nn mean AP
+# ------------------------------------------------------------------------------------------------
+def _f64(t: Tensor, name: str) -> Tensor:
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.DfepeError(f"{name} must live on the GPU (this package has no CPU path)")
+    return t.to(torch.float64).contiguous()  # float32 -> float64 is exact
+
+
+def keypoint_repeatability(kp1: Tensor, kp2: Tensor, H: Tensor, height: int, width: int, keep_k: int, thresh: Tensor,
+                           n1: Optional[Tensor] = None, n2: Optional[Tensor] = None) -> dict:
+    """kp1 [B,N1,C], kp2 [B,N2,C] rows (x, y[, prob]) of image 1 and image 2, C in {2, 3}; H [B,3,3] image 1 -> image 2; thresh [T]
+    on the device -> compute_repeatability (evaluations/detector_evaluation.py:150-279) of every pair at every threshold, in fp64
+    (float32 inputs are upcast, which is exact).  n1, n2 [B] int32 on the device or None: pair b uses its first n[b] rows.
+    Returns dict(repeatability, loc_err [B,T] float64 (0 and -1 where nothing is counted), count1, count2 [B,T] int32, kept1, kept2
+    [B] int32 (the set sizes after the filter and select_k_best), n_unwarped [B] int32 (the matching score's count of image-2
+    points whose inverse warp lies in the image, both ends inclusive)).  Equal probabilities at the k-th place: the higher index
+    is kept; keep_k = 0 keeps every point (numpy's [-0:]).  The inputs are not written to.  No host synchronisation.
+    N1, N2 <= 4096."""
+    a, b = _f64(kp1, "kp1"), _f64(kp2, "kp2")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2] or a.shape[2] not in (2, 3):
+        raise ValueError(f"keypoints must be [B,N1,C] and [B,N2,C] with C in (2, 3), got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, N1, C = a.shape
+    N2 = b.shape[1]
+    if max(N1, N2) > _lib.DETECTOR_EVAL_MAX_N:
+        raise _lib.DfepeError(f"keypoint_repeatability: {max(N1, N2)} keypoints per image; at most {_lib.DETECTOR_EVAL_MAX_N}")
+    if int(keep_k) < 0 or int(height) < 1 or int(width) < 1:
+        raise ValueError("keypoint_repeatability: keep_k must be >= 0, height and width >= 1")
+    Hd = _h9(H, "H", B)
+    dev = a.device
+    if not torch.is_tensor(thresh) or not thresh.is_cuda or thresh.dim() != 1:
+        raise _lib.DfepeError("keypoint_repeatability: thresh must be a 1-D tensor on the GPU")
+    th = thresh.to(torch.float64).contiguous()
+    T = th.shape[0]
+    c1, c2 = _n_valid_arg(n1, B, dev, "keypoint_repeatability"), _n_valid_arg(n2, B, dev, "keypoint_repeatability")
+    L = _lib.lib()
+    ws = torch.empty(max(1, (int(L.dfepe_keypoint_repeatability_workspace_bytes(B, N1, N2)) + 15) // 16), 2, dtype=torch.float64, device=dev)
+    out = {
+        "repeatability": torch.empty(B, T, device=dev, dtype=torch.float64),
+        "loc_err": torch.empty(B, T, device=dev, dtype=torch.float64),
+        "count1": torch.empty(B, T, device=dev, dtype=torch.int32),
+        "count2": torch.empty(B, T, device=dev, dtype=torch.int32),
+        "kept1": torch.empty(B, device=dev, dtype=torch.int32),
+        "kept2": torch.empty(B, device=dev, dtype=torch.int32),
+        "n_unwarped": torch.empty(B, device=dev, dtype=torch.int32),
+    }
+    with _on(dev):
+        rc = L.dfepe_keypoint_repeatability(_ptr(a), _ptr(b), _ptr(c1), _ptr(c2), _ptr(Hd), B, N1, N2, C, int(height), int(width), int(keep_k),
+                                            _ptr(th), T, _ptr(ws), _ptr(out["repeatability"]), _ptr(out["loc_err"]), _ptr(out["count1"]),
+                                            _ptr(out["count2"]), _ptr(out["kept1"]), _ptr(out["kept2"]), _ptr(out["n_unwarped"]), _stream())
+    _lib.check(rc, "dfepe_keypoint_repeatability")
+    return out
+
+
+def average_precision(labels: Tensor, scores: Tensor, n_valid: Optional[Tensor] = None, want_counts: bool = False) -> dict:
+    """labels [B,M] (non-zero: positive), scores [B,M] -> sklearn.metrics.average_precision_score of every pair
+    (evaluate_frontend.py:244-275) as AP = (1/P) sum over positives of TP(s_i) / CNT(s_i), which groups tied scores as scikit-learn
+    does and needs no sort.  n_valid [B] int32 on the device or None.  Returns dict(ap [B] float64 (0 without a valid entry or a
+    positive), n_pos [B] int32, tp_at, cnt_at [B,M] int32 | None (want_counts; 0 past n_valid)).  No host synchronisation.
+    M <= 4096."""
+    sc = _f64(scores, "scores")
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise _lib.DfepeError("labels must live on the GPU (this package has no CPU path)")
+    if sc.dim() != 2 or labels.shape != sc.shape:
+        raise ValueError(f"labels and scores must both be [B,M], got {tuple(labels.shape)} and {tuple(sc.shape)}")
+    B, M = sc.shape
+    if M > _lib.DETECTOR_EVAL_MAX_N:
+        raise _lib.DfepeError(f"average_precision: {M} entries per pair; at most {_lib.DETECTOR_EVAL_MAX_N}")
+    lb = (labels != 0).to(torch.uint8).contiguous()
+    dev = sc.device
+    nv = _n_valid_arg(n_valid, B, dev, "average_precision")
+    out = {
+        "ap": torch.empty(B, device=dev, dtype=torch.float64),
+        "n_pos": torch.empty(B, device=dev, dtype=torch.int32),
+        "tp_at": torch.empty(B, M, device=dev, dtype=torch.int32) if want_counts else None,
+        "cnt_at": torch.empty(B, M, device=dev, dtype=torch.int32) if want_counts else None,
+    }
+    with _on(dev):
+        rc = _lib.lib().dfepe_average_precision(_ptr(lb), _ptr(sc), _ptr(nv), B, M, _ptr(out["ap"]), _ptr(out["n_pos"]), _ptr(out["tp_at"]),
+                                                _ptr(out["cnt_at"]), _stream())
+    _lib.check(rc, "dfepe_average_precision")
+    return out
+
+
+def matching_score(n_inliers: Tensor, n_kp1: Tensor, n_unwarped: Tensor) -> Tensor:
+    """n_inliers, n_kp1, n_unwarped [B] integer tensors on the device -> mscore [B] float64 = 2 n_inliers / (n_kp1 + n_unwarped)
+    (evaluate_frontend.py:181); a zero denominator gives what the division gives.  No host synchronisation."""
+    args = []
+    for t, name in ((n_inliers, "n_inliers"), (n_kp1, "n_kp1"), (n_unwarped, "n_unwarped")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.DfepeError(f"{name} must live on the GPU (this package has no CPU path)")
+        if t.dim() != 1 or t.shape != n_inliers.shape or t.dtype.is_floating_point:
+            raise ValueError(f"{name} must be an integer tensor of shape [{n_inliers.shape[0]}], got {t.dtype} {tuple(t.shape)}")
+        args.append(t.to(torch.int32).contiguous())
+    B = args[0].shape[0]
+    dev = args[0].device
+    out = torch.empty(B, device=dev, dtype=torch.float64)
+    with _on(dev):
+        rc = _lib.lib().dfepe_matching_score(_ptr(args[0]), _ptr(args[1]), _ptr(args[2]), B, _ptr(out), _stream())
+    _lib.check(rc, "dfepe_matching_score")
+    return out
