@@ -61,6 +61,35 @@ static_assert(S16_Q == 8 && S16_INVTR < S16_Q && S16_TD >= S16_Q + 64 && S16_TD 
               S16_Z >= S16_LAM + 2 && S16_S3 < S16_MARK && S16_TAG == DFEPE_SAVE_FLOATS - 1,
               "slices 1..8 of the record hold the rows of Q' only; the fp64 pieces are 8-byte aligned; nothing overlaps");
 
+// The record as the backward holds it: lane l of the row has floats 8 l .. 8 l + 7 in `slice` (two 16-byte loads per lane bring in all
+// 512 bytes), and float IDX comes to every lane of the row from lane IDX >> 3, slot IDX & 7, by one in-row broadcast.  A global load
+// instruction costs a lone wavefront 50-70 cycles whatever it fetches, a broadcast ~5: a piece the whole row shares is not loaded by
+// each of its lanes.  All lanes of the row must reach the call together.  rec_d: an fp64 piece (8-byte aligned: both halves in one lane).
+template <int IDX>
+__device__ __forceinline__ float rec_f(const float* slice) {
+  static_assert(IDX >= 0 && IDX < DFEPE_SAVE_FLOATS, "float of the record");
+  return rg_bcast<(IDX >> 3)>(slice[IDX & 7]);
+}
+template <int IDX>
+__device__ __forceinline__ double rec_d(const float* slice) {
+  static_assert(IDX >= 0 && IDX + 1 < DFEPE_SAVE_FLOATS && IDX % 2 == 0, "8-byte aligned fp64 piece of the record");
+  double v;
+  __builtin_memcpy(&v, slice + (IDX & 7), sizeof(double));
+  return rg_bcast<(IDX >> 3)>(v);
+}
+// The same piece for either way the backward holds the record: SLICED from the row's slices (all lanes of the row together), otherwise
+// straight from the record at `rec` -- for a pair that is uniform over the wavefront, where that is a scalar load and costs no VGPR.
+template <int IDX, bool SLICED>
+__device__ __forceinline__ float rec_f(const float* slice, const float* rec) {
+  if constexpr (SLICED) return rec_f<IDX>(slice);
+  else return rec[IDX];
+}
+template <int IDX, bool SLICED>
+__device__ __forceinline__ double rec_d(const float* slice, const float* rec) {
+  if constexpr (SLICED) return rec_d<IDX>(slice);
+  else return reinterpret_cast<const double*>(rec + IDX)[0];
+}
+
 struct W8Args {
   const float* pts1;
   const float* pts2;
@@ -287,7 +316,8 @@ __device__ __forceinline__ double pivot_guard(double q) { return (fabs(q) < 1e-3
 
 // y = diag(1, Q') x for a vector x the whole row shares: lane i (1..8) forms component i from its own row of Q' -- two independent
 // accumulators, no exchange -- and nine broadcasts make the result uniform again.  (The forward's f = Q z, the backward's f = Q z
-// and u = Q y; the lanes outside 1..8 compute something nobody reads.)
+// and u = Q y; the lanes outside 1..8 compute something nobody reads: in the backward their Qr holds other pieces of the record, so
+// nothing here or in rg_dot_bcast<1>(Qr[c], ..) may come to read Qr outside lanes 1..8.)
 __device__ __forceinline__ void basis_apply(const double* Qr, const double* x, double* y) {
   const double e = fma(Qr[7], x[7], fma(Qr[5], x[5], fma(Qr[3], x[3], Qr[1] * x[1])));
   const double o = fma(Qr[8], x[8], fma(Qr[6], x[6], fma(Qr[4], x[4], Qr[2] * x[2])));

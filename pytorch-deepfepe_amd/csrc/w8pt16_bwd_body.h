@@ -138,38 +138,62 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
   const float* sv = A.save + (size_t)pair * DFEPE_SAVE_FLOATS;
 
   DFEPE_MARK("B0_load");
-  // ---- the forward's record (row-uniform loads) and the pair's correspondences -------------------------------
-  const double s1 = sv[S16_T1], c1x = sv[S16_T1 + 1], c1y = sv[S16_T1 + 2];
-  const double s2 = sv[S16_T2], c2x = sv[S16_T2 + 1], c2y = sv[S16_T2 + 2];
-  double f[9], z[9], td[9], te[8], Qr[9];
-#pragma unroll
-  for (int c = 0; c < 9; ++c) { z[c] = sv[S16_Z + c]; td[c] = reinterpret_cast<const double*>(sv + S16_TD)[c]; }
-#pragma unroll
-  for (int c = 0; c < 8; ++c) te[c] = reinterpret_cast<const double*>(sv + S16_TE)[c];
+  // ---- the forward's record and the pair's correspondences ---------------------------------------------------
+  // A row per pair (ROWS = 1): the record arrives in lane slices.  Lane l loads floats 8 l .. 8 l + 7 (two 16-byte loads: the row's
+  // 16 lanes bring in all 512 bytes), and every piece the row shares is then one in-row broadcast from the lane that holds it (rec_f
+  // / rec_d, w8pt16_body.h).  Lanes 1..8 keep their slice as their row of Q'; the other lanes' Qr holds other pieces of the record and
+  // is never read (basis_apply and rg_dot_bcast<1> take lanes 1..8 only).  g_F (and F_out, for pass A) likewise: lane c < 9 loads
+  // entry c, the other lanes entry 8 again.
+  // A workgroup per pair (ROWS = 16): the pair is uniform over the wavefront, so the shared pieces are scalar loads into SGPRs, which
+  // cost neither vector registers nor vector-memory issue; broadcasts would take both (IT = 8: 225 -> 271 registers, one workgroup
+  // per CU instead of two).  There the lanes outside 1..8 load row 1 of Q' and only the Q' rows come by vector loads.
+  constexpr bool SL = ROWS == 1;
+  float sl[8];
   {
-    // the lane's row of Q' (lanes 1..8; the others read row 1 and use nothing of it): slice l of the record, two 16-byte loads
-    // from an index-clamped address, unconditional like every other load of this block
-    const int lq = (l >= 1 && l <= 8) ? l : 1;
+    const int lq = (SL || (l >= 1 && l <= 8)) ? l : 1;
     const float4* qp = reinterpret_cast<const float4*>(static_cast<const float*>(__builtin_assume_aligned(A.save, 16)) +
                                                        (size_t)pair * DFEPE_SAVE_FLOATS + 8 * lq);
     const float4 q0 = qp[0], q1 = qp[1];
-    Qr[0] = 0.0;
-    Qr[1] = q0.x; Qr[2] = q0.y; Qr[3] = q0.z; Qr[4] = q0.w;
-    Qr[5] = q1.x; Qr[6] = q1.y; Qr[7] = q1.z; Qr[8] = q1.w;
+    sl[0] = q0.x; sl[1] = q0.y; sl[2] = q0.z; sl[3] = q0.w;
+    sl[4] = q1.x; sl[5] = q1.y; sl[6] = q1.z; sl[7] = q1.w;
   }
-  const double lam = reinterpret_cast<const double*>(sv + S16_LAM)[0];
   // d loss / d F_out and its scale: loaded here (null-safe addresses) with everything else, not where they are first used
-  float gF_in[9];
-  {
-    const float* gp = (A.g_F != nullptr) ? A.g_F + (size_t)pair * 9 : sv + S16_Z;
-#pragma unroll
-    for (int c = 0; c < 9; ++c) gF_in[c] = gp[c];
-  }
+  const float* gF_p = (A.g_F != nullptr) ? A.g_F + (size_t)pair * 9 : sv + S16_Z;
+  const int l9 = (l < 9) ? l : 8;
+  float gF_l = 0.0f, Fo_l = 0.0f;
+  if constexpr (SL) gF_l = gF_p[l9];
+  if constexpr (SL && UP) Fo_l = ((A.g_epi != nullptr) ? A.F_out + (size_t)pair * 9 : sv + S16_Z)[l9];
   const float gs_in = ((A.g_scale != nullptr) ? A.g_scale : sv + S16_TAG)[l & 0];  // a vector load: the scalar cache would miss
-  const int twist = (int)sv[S16_TWIST];
-  const double inv_tr = sv[S16_INVTR];
+  const double s1 = rec_f<S16_T1, SL>(sl, sv), c1x = rec_f<S16_T1 + 1, SL>(sl, sv), c1y = rec_f<S16_T1 + 2, SL>(sl, sv);
+  const double s2 = rec_f<S16_T2, SL>(sl, sv), c2x = rec_f<S16_T2 + 1, SL>(sl, sv), c2y = rec_f<S16_T2 + 2, SL>(sl, sv);
+  double f[9], z[9], td[9], te[8], Qr[9];
+  static_for<0, 9>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    z[c] = rec_f<S16_Z + c, SL>(sl, sv);
+    td[c] = rec_d<S16_TD + 2 * c, SL>(sl, sv);
+  });
+  static_for<0, 8>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    te[c] = rec_d<S16_TE + 2 * c, SL>(sl, sv);
+  });
+  Qr[0] = 0.0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) Qr[1 + c] = sl[c];
+  const double lam = rec_d<S16_LAM, SL>(sl, sv);
+  float gF_in[9];
+  static_for<0, 9>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    if constexpr (SL) gF_in[c] = rg_bcast<c>(gF_l);
+    else gF_in[c] = gF_p[c];
+  });
+  const int twist = (int)rec_f<S16_TWIST, SL>(sl, sv);
+  const double inv_tr = rec_f<S16_INVTR, SL>(sl, sv);
   // a record of another layout would be misread: poison instead.  The tag alone cannot tell the reflector layout from this one.
-  const bool good = sv[S16_TAG] == S16_TAG_VALUE && sv[S16_MARK] == S16_MARK_VALUE;
+  // In lane slices, lane 15 holds both marks: it compares, the row takes its verdict.
+  static_assert((S16_TAG >> 3) == 15 && (S16_MARK >> 3) == 15, "tag and mark sit in lane 15's slice");
+  bool good;
+  if constexpr (SL) good = rg_bcast<15>((sl[S16_TAG & 7] == S16_TAG_VALUE && sl[S16_MARK & 7] == S16_MARK_VALUE) ? 1 : 0) != 0;
+  else good = sv[S16_TAG] == S16_TAG_VALUE && sv[S16_MARK] == S16_MARK_VALUE;
 
   // same unconditional loads and the same drop rule as the forward (w8pt16_fwd_pair, phase 0); IT = 0: any N, re-read per pass
   constexpr int ITR = (IT > 0) ? IT : 1;
@@ -207,7 +231,8 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
   // (round 6, scripts/ubench/bwd_phases.hip: this block -- ~50 load instructions, no wait inside it -- is 23 % of the g_F-only kernel:
   // a lone wavefront pays ~60 cycles per VMEM instruction it ISSUES while every CU is loading.  Keeping the correspondences raw until
   // pass B, so that the uniform part runs under their arrival, changed nothing: 3059 vs 3064 cycles, same 250 registers -- the data
-  // is back long before the rank-2 adjoint needs it; what costs is the instruction issue itself.)
+  // is back long before the rank-2 adjoint needs it; what costs is the instruction issue itself.  Hence the record in lane slices
+  // above, for the row kernels: 39 -> 18 load instructions in the g_F-only build, 11 984 -> 10 462 cycles, profiles/row_shared_loads.md.)
   if constexpr (IT > 0) {
     static_for<0, IT>([&](auto c) {
       constexpr int it = decltype(c)::value;
@@ -245,9 +270,12 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
   double gx[9], go[9], o[9];
 #pragma unroll
   for (int c = 0; c < 9; ++c) { gx[c] = 0.0; go[c] = 0.0; o[c] = 0.0; }
-  if (A.g_epi != nullptr) {
-#pragma unroll
-    for (int c = 0; c < 9; ++c) o[c] = (double)A.F_out[(size_t)pair * 9 + c];
+  if (A.g_epi != nullptr) {  // the same way for every lane of the launch
+    static_for<0, 9>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      if constexpr (SL) o[c] = (double)rg_bcast<c>(Fo_l);
+      else o[c] = (double)A.F_out[(size_t)pair * 9 + c];
+    });
   }
   if (A.g_res != nullptr || A.g_epi != nullptr) {
     float gxf[9], gof[9];
@@ -332,9 +360,12 @@ __device__ __forceinline__ void w8pt16_bwd_pair_impl(const W8BwdArgs& A0, const 
   DFEPE_MARK("B2_uniform");
   double u[9];
   double u3[3], v3[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) { u3[c] = sv[S16_U3 + c]; v3[c] = sv[S16_V3 + c]; }
-  const double s3 = sv[S16_S3];
+  static_for<0, 3>([&](auto cc) {
+    constexpr int c = decltype(cc)::value;
+    u3[c] = rec_f<S16_U3 + c, SL>(sl, sv);
+    v3[c] = rec_f<S16_V3 + c, SL>(sl, sv);
+  });
+  const double s3 = rec_f<S16_S3, SL>(sl, sv);
   basis_apply(Qr, z, f);  // f = Q z: the record holds z and Q, not f (every row of a cooperative workgroup, for pass B)
   if (ROWS == 1 || rowid == 0) {
   // ---- uniform part (one row per pair) ------------------------------------------------------------------------
