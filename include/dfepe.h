@@ -102,6 +102,38 @@ int dfepe_w8pt_fwd(const float *pts1, const float *pts2, const float *weights, i
                    float *F_out, float *residual, float *epi_res, float *save, float *weights_out, void *stream);
 
 /*
+ * The same fit, handing the Hartley transforms of Fit.normalize from one launch to later ones.  Fit.normalize is unweighted: the
+ * centroids and the scales 1.4142 / mean distance depend on the correspondences alone, so a step that fits the SAME matches at
+ * several layers (every layer of pipeline.hot_path_fused; the recurrent model while it learns no offsets) computes them once.
+ *   hartley      [B,DFEPE_HARTLEY_DOUBLES] doubles, 64-byte aligned: one record per pair of the B sets of correspondences (not per
+ *                weight set); opaque, and like `save` it never outlives the step that wrote it
+ *   hartley_mode DFEPE_HARTLEY_NONE   `hartley` is ignored (may be NULL): this call IS dfepe_w8pt_fwd
+ *                DFEPE_HARTLEY_WRITE  the launch computes the transforms as always and also stores them (as fp64) in `hartley`
+ *                DFEPE_HARTLEY_READ   the launch takes them from `hartley` instead of computing them
+ * Every output is bit-identical in the three modes.
+ * Contract: a reader must be given the same correspondences (pts1, pts2, B, N), the same image size and the same Hartley-affecting
+ * flags (DFEPE_W8PT_RAW_MATCHES, DFEPE_W8PT_SQRT2, DFEPE_W8PT_NO_HARTLEY) as the writer, and the writer must come earlier on the
+ * same stream.  Weights, DFEPE_W8PT_LOGITS and n_weight_sets may differ.  A reader that is handed a record no writer filled
+ * returns NaN outputs instead of misreading it.
+ * Where dfepe_w8pt_shares_hartley(N, flags) is 0 -- N > DFEPE_W8PT16_MAX_N, or DFEPE_W8PT_NO_HARTLEY -- both modes are ignored:
+ * nothing is written, nothing is read, and the launch is that of dfepe_w8pt_fwd.  The answer depends on N and the flags only, never
+ * on B, so a writer and its readers always agree.  DFEPE_HARTLEY_SHARE=0 in the environment (read once; A/B timing on one build)
+ * makes this entry point ignore the record in both modes.
+ * Errors (before any HIP call): a mode outside 0..2, or a non-zero mode with a NULL or misaligned `hartley`: DFEPE_ERR_INVALID_ARG
+ * (checked first, whatever the shape and the switch above); then those of dfepe_w8pt_fwd.  B = 0 returns DFEPE_OK.
+ * dfepe_version() stays 154 with this addition: the number is pinned by existing tests, and nothing that existed changes.
+ */
+#define DFEPE_HARTLEY_DOUBLES 8
+#define DFEPE_HARTLEY_NONE 0
+#define DFEPE_HARTLEY_WRITE 1
+#define DFEPE_HARTLEY_READ 2
+int dfepe_w8pt_fwd_shared(const float *pts1, const float *pts2, const float *weights, int B, int N, int n_weight_sets,
+                          unsigned flags, float image_w, float image_h, float clamp_at,
+                          float *F_out, float *residual, float *epi_res, float *save, float *weights_out,
+                          double *hartley, int hartley_mode, void *stream);
+int dfepe_w8pt_shares_hartley(int N, unsigned flags); /* 1 where a launch of this shape writes / reads the record */
+
+/*
  * Backward of dfepe_w8pt_fwd w.r.t. the weights (analytic eigenvector / rank-2 / epipolar-residual
  * adjoints; replaces torch.autograd through the per-sample torch.svd calls, DeepFNet.py:232-256).
  *   g_F [B,9], g_residual [B,N], g_epi [B,N]: upstream gradients, each may be NULL (= zero)

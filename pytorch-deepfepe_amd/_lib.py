@@ -22,6 +22,8 @@ W8PT_FORCE_110 = 16
 W8PT_NO_HARTLEY = 32
 W8PT_ROW_PER_PAIR = 64
 W8PT16_MAX_N = 128
+HARTLEY_DOUBLES = 8  # dfepe_w8pt_fwd_shared: doubles per pair in the Hartley record (64-byte aligned)
+HARTLEY_NONE, HARTLEY_WRITE, HARTLEY_READ = 0, 1, 2  # ... and its modes
 TAIL_MAX_LAYERS = 16  # dfepe_loss_tail: layers per launch (kTailMaxLayers, csrc/loss_tail_body.h)
 EPI_HOMOGENEOUS = 8
 CHEIR_FP64_ONLY = 1
@@ -47,6 +49,8 @@ _SIGNATURES = {
     "dfepe_save_floats": (c_int, []),
     "dfepe_selftest_rowgroup": (c_int, [_P, _P, _P, _P]),
     "dfepe_w8pt_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_uint, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "dfepe_w8pt_fwd_shared": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_uint, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "dfepe_w8pt_shares_hartley": (c_int, [c_int, c_uint]),
     "dfepe_w8pt_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_uint, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dfepe_w8pt_rows_fwd": (c_int, [_P, c_int, c_int, c_uint, _P, _P, _P, _P]),
     "dfepe_floss_fwd": (c_int, [_P, c_int, c_int, _P, _P, c_int, _P, _P, _P, c_int, c_float, _P, _P, _P]),

@@ -99,6 +99,9 @@ class DeepFNet(nn.Module):
         self.input_weights = Est(4 + quality_size)
         self.update_weights = Est(4 + quality_size + 3)  # + weights, epi_res, residual (DeepFNet.py:340)
         self.if_learn_offsets = if_learn_offsets
+        # the fits of layers 2..L take the Hartley transforms of layer 1's fit while the matches stay the same (_forward); the
+        # numbers are the same bit for bit, False computes them at every layer (A/B timing, tests)
+        self.share_hartley = bool(params.get("share_hartley", True))
         if if_learn_offsets:  # (DeepFNet.py:341-342): per-correspondence pixel offsets, no batch norm
             self.update_offsets = Est(4 + quality_size + 3, output_size=4, if_bn=False)
         if is_test:
@@ -171,12 +174,15 @@ class DeepFNet(nn.Module):
         """logits [B,1,N] -> (out, residual[, epi], weights_prod [B,1,N]).  The softmax over N is fused into the solver
         kernel unless per-correspondence image weights multiply it afterwards (if_img_w).  ``dst``: rows of the per-layer
         stacks the outputs are written into (ops.w8pt_forward), so that the loss functions find every layer's F, epipolar
-        residual and weights in one buffer each (no torch.stack copies, train_good_utils.get_all_loss_DeepF)."""
+        residual and weights in one buffer each (no torch.stack copies, train_good_utils.get_all_loss_DeepF).
+        While every layer fits the same matches, _forward leaves (record, mode) of ops.w8pt_forward in ``self._hartley`` for the
+        call (instance state, not an argument: callers wrap this method with its five-argument signature)."""
         H, W = float(self.image_size[0]), float(self.image_size[1])
+        hartley = getattr(self, "_hartley", None)
         if self.if_img_w:
             weights_prod = F.softmax(logits, dim=2) * data_batch["weights_im"]
-            return ops.w8pt_raw(matches, weights_prod, W, H, clamp_at=0.5, want_epi=want_epi) + (weights_prod,)
-        outs = ops.w8pt_raw_logits(matches, logits, W, H, clamp_at=0.5, want_epi=want_epi, dst=dst)
+            return ops.w8pt_raw(matches, weights_prod, W, H, clamp_at=0.5, want_epi=want_epi, hartley=hartley) + (weights_prod,)
+        outs = ops.w8pt_raw_logits(matches, logits, W, H, clamp_at=0.5, want_epi=want_epi, dst=dst, hartley=hartley)
         return outs[:-1] + (outs[-1].unsqueeze(1),)
 
     def forward(self, data_batch):
@@ -213,8 +219,21 @@ class DeepFNet(nn.Module):
                 d.update({"weights": (stores[l], c0), "epi": (stores[l], c0 + 1), "residual": (stores[l], c0 + 2)})
             return d
 
+        # Without learned offsets every layer fits the same matches, and Fit.normalize is unweighted (image weights do not enter
+        # it either): the first fit writes its Hartley transforms, the later ones read them (ops.w8pt_forward; the same bits).
+        record = None
+        if getattr(self, "share_hartley", True) and not self.if_learn_offsets and self.depth > 1 and _lib.lib().dfepe_w8pt_shares_hartley(N, 0) == 1:
+            record = ops.hartley_record(B, dev)
+
+        def fit(l, logits, want_epi):
+            self._hartley = None if record is None else (record, _lib.HARTLEY_WRITE if l == 0 else _lib.HARTLEY_READ)
+            try:
+                return self._fit(matches, logits, data_batch, want_epi, dst(l))
+            finally:
+                self._hartley = None
+
         for it in range(self.depth - 1):
-            out, residual, epi, weights_prod = self._fit(matches, logits, data_batch, True, dst(it))
+            out, residual, epi, weights_prod = fit(it, logits, True)
             weights_layers.append(weights_prod)
             out_layers.append(out)
             residual_layers.append(residual)
@@ -231,7 +250,7 @@ class DeepFNet(nn.Module):
                 net_in = torch.cat((pts_normalized_in, weights_prod, epi_res, residual.unsqueeze(1)), 1)
             logits = self.update_weights(net_in)
             logits_layers.append(logits)
-        out, residual, weights_prod = self._fit(matches, logits, data_batch, False, dst(self.depth - 1))
+        out, residual, weights_prod = fit(self.depth - 1, logits, False)
         weights_layers.append(weights_prod)
         residual_layers.append(residual)
         out_layers.append(out)

@@ -72,6 +72,13 @@ constexpr FitPlan fit_fwd_plan(int N, int pairs, bool raw, bool row_per_pair, in
   return {N > 64 && fit_switch(force_lean, pairs >= kLeanMinPairs) ? FitKind::RowLean : FitKind::Row, fit_it(N)};
 }
 
+// Does a forward launch of this shape write / read the Hartley record (dfepe_w8pt_fwd_shared)?  The registers-resident row kernels
+// do -- every rung of fit_it, resident and lean -- unless the fit has no Hartley normalisation to hand on.  For N > 128 (cooperative,
+// two-row and looped kernels) the record would remove one or two of four passes over the correspondences: not built.  The answer
+// depends on N and the flags alone, never on the pair count or the environment, so a writer and its readers always agree.
+// no_hartley: DFEPE_W8PT_NO_HARTLEY is set
+constexpr bool fit_shares_hartley(int N, bool no_hartley) { return fit_it(N) > 0 && !no_hartley; }
+
 // pgrad: point gradients wanted; plain: no variant flag; gF_only: neither g_residual nor g_epi nor g_weights_extra given
 constexpr FitPlan fit_bwd_plan(int N, int pairs, bool row_per_pair, bool pgrad, bool plain, bool gF_only) {
   if (!pgrad && plain && fit_coop_serves(N, pairs, row_per_pair)) return {FitKind::Coop, coop_it(N)};

@@ -28,10 +28,12 @@ struct W8FwdRest {
   float* weights_out;
   int logits_mode;
   unsigned variant;
+  double* hartley;  // the Hartley record and its mode (w8pt16_body.h): read by the *_shared kernels only, behind everything the others take
+  int hartley_mode;
 };
 // (the Rest structs, their split and their fill live here and not beside W8Args / W8BwdArgs: only these kernels take them, and
 // their unnamed-namespace type is part of the kernels' symbol names)
-W8FwdRest rest_of(const W8Args& A) { return {A.epi_res, A.save, A.weights_out, A.logits_mode, A.variant}; }
+W8FwdRest rest_of(const W8Args& A) { return {A.epi_res, A.save, A.weights_out, A.logits_mode, A.variant, A.hartley, A.hartley_mode}; }
 // ... and put together again in the kernel
 __device__ __forceinline__ W8Args w8_args(const float* pts1, const float* pts2, const float* wts, int B, int Bm, int N, float hw_sx, float hw_sy,
                                           float clamp_at, float* F_out, float* residual, const W8FwdRest& R) {
@@ -39,6 +41,7 @@ __device__ __forceinline__ W8Args w8_args(const float* pts1, const float* pts2, 
   A.pts1 = pts1; A.pts2 = pts2; A.wts = wts; A.B = B; A.Bm = Bm; A.N = N; A.hw_sx = hw_sx; A.hw_sy = hw_sy;
   A.clamp_at = clamp_at; A.F_out = F_out; A.residual = residual; A.epi_res = R.epi_res; A.save = R.save;
   A.weights_out = R.weights_out; A.logits_mode = R.logits_mode; A.variant = R.variant; A.row_per_pair = false;
+  A.hartley = R.hartley; A.hartley_mode = R.hartley_mode;
   return A;
 }
 
@@ -97,6 +100,35 @@ w8pt16_fwd_lean_kernel(const float* pts1, const float* pts2, const float* wts, i
   if (pair >= B) return;
   const W8Args A = w8_args(pts1, pts2, wts, B, Bm, N, hw_sx, hw_sy, clamp_at, F_out, residual, R);
   w8pt16_fwd_pair<IT, RAW, PLAIN, 1, true>(A, pair, xch + row * 36);
+}
+
+// The two kernels above with the Hartley record (w8pt16_body.h: HM = H16_BY_LAUNCH): layer 1 of a step that fits the same matches at
+// every layer writes the transforms, layers 2..L read them.  Kernels of their own, so that a launch without a record runs the very
+// code it ran before the record existed; ONE kernel for the writer and its readers, so that the readers find its code in the cache.
+template <int IT, bool RAW, bool PLAIN>
+__global__ void __launch_bounds__(256)
+w8pt16_fwd_shared_kernel(const float* pts1, const float* pts2, const float* wts, int B, int Bm, int N, float hw_sx, float hw_sy,
+                         float clamp_at, float* F_out, float* residual, const W8FwdRest R) {
+  __shared__ double xch[kPairsPerBlock * 36];
+  const int row = (int)(threadIdx.x >> 4);
+  const int pair = (int)blockIdx.x * kPairsPerBlock + row;
+  if (pair >= B) return;
+#if DFEPE_FWD_STAGGER
+  for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) DFEPE_STAGGER_WAIT(DFEPE_FWD_STAGGER);
+#endif
+  const W8Args A = w8_args(pts1, pts2, wts, B, Bm, N, hw_sx, hw_sy, clamp_at, F_out, residual, R);
+  w8pt16_fwd_pair<IT, RAW, PLAIN, 1, false, H16_BY_LAUNCH>(A, pair, xch + row * 36);
+}
+template <int IT, bool RAW, bool PLAIN>
+__global__ void __launch_bounds__(256, 2)
+w8pt16_fwd_lean_shared_kernel(const float* pts1, const float* pts2, const float* wts, int B, int Bm, int N, float hw_sx, float hw_sy,
+                              float clamp_at, float* F_out, float* residual, const W8FwdRest R) {
+  __shared__ double xch[kPairsPerBlock * 36];
+  const int row = (int)(threadIdx.x >> 4);
+  const int pair = (int)blockIdx.x * kPairsPerBlock + row;
+  if (pair >= B) return;
+  const W8Args A = w8_args(pts1, pts2, wts, B, Bm, N, hw_sx, hw_sy, clamp_at, F_out, residual, R);
+  w8pt16_fwd_pair<IT, RAW, PLAIN, 1, true, H16_BY_LAUNCH>(A, pair, xch + row * 36);
 }
 
 // N > 128 at a few thousand pairs: TWO rows of a wavefront per pair (w8pt16_body.h: ROWS = 2).  One row per pair is one wavefront per
@@ -259,6 +291,11 @@ bool launch_fwd(const W8Args& A, hipStream_t st) {
   if (p.kind == FitKind::Pair2) {
     if constexpr (RAW) go(w8pt16_pair2_fwd_kernel<true, PLAIN>, blocks_of(A.B, kPairsPerBlock2));
     return RAW;
+  }
+  // with the Hartley record (A.hartley_mode is set only where fit_shares_hartley holds: a row kernel with p.it > 0)
+  if (A.hartley_mode != DFEPE_HARTLEY_NONE) {
+    if (p.kind == FitKind::RowLean) return with_it_in<7, 8>(p.it, [&](auto it) { go(w8pt16_fwd_lean_shared_kernel<it.value, RAW, PLAIN>, rows); });
+    return with_it_in<1, 2, 4, 7, 8>(p.it, [&](auto it) { go(w8pt16_fwd_shared_kernel<it.value, RAW, PLAIN>, rows); });
   }
   if (p.it < 7) return with_it_in<0, 1, 2, 4>(p.it, row);
   // 7 or 8 correspondences per lane: the two rungs that have a lean build

@@ -90,6 +90,24 @@ __device__ __forceinline__ double rec_d(const float* slice, const float* rec) {
   else return reinterpret_cast<const double*>(rec + IDX)[0];
 }
 
+// ---- the Hartley record (doubles; DFEPE_HARTLEY_DOUBLES = 8 per pair of correspondences, 64-byte aligned) ---------------
+// Fit.normalize is unweighted: the centroids and scales depend on the correspondences alone, so the fits of layers 2..L of a step
+// that refits the same matches take them from layer 1 instead of recomputing the centroid pass and phase 1.  The six values are the
+// fp64 values the writer's body holds when phase 1 ends (the floats S16_T1 / S16_T2 of the `save` record are rounded and would change
+// every output bit); a reader broadcasts them in-row, so its outputs are those of a launch that computed them.  Lane l < 8 of the row
+// writes / reads slot l.  Like the `save` record it never outlives the step that wrote it, and a reader that is handed anything
+// else (a tag that is not H16_TAG_VALUE) turns s1 into NaN and so poisons its outputs instead of misreading the record.
+#define H16_C1X 0
+#define H16_C1Y 1
+#define H16_S1 2
+#define H16_C2X 3
+#define H16_C2Y 4
+#define H16_S2 5
+                      // slot 6: unused (zero)
+#define H16_TAG 7
+#define H16_TAG_VALUE 29.0
+static_assert(DFEPE_HARTLEY_DOUBLES == 8 && H16_TAG == DFEPE_HARTLEY_DOUBLES - 1, "one slot per lane of a half-row");
+
 struct W8Args {
   const float* pts1;
   const float* pts2;
@@ -104,6 +122,8 @@ struct W8Args {
   int logits_mode;
   unsigned variant;
   bool row_per_pair;  // host side only: never the cooperative workgroup (DFEPE_W8PT_ROW_PER_PAIR)
+  double* hartley;    // [Bm, DFEPE_HARTLEY_DOUBLES] or null: the Hartley record (touched by the HM != 0 instantiations only)
+  int hartley_mode;   // DFEPE_HARTLEY_NONE / WRITE / READ, already cleared where fit_shares_hartley says no (read by HM = H16_BY_LAUNCH)
 };
 
 // host side: the (validated) arguments of dfepe_w8pt_fwd as the kernels take them
@@ -119,6 +139,7 @@ inline W8Args w8_args_of(const float* pts1, const float* pts2, const float* weig
   A.logits_mode = (flags & DFEPE_W8PT_LOGITS) ? 1 : 0;
   A.variant = flags & (DFEPE_W8PT_SQRT2 | DFEPE_W8PT_NO_ROWNORM | DFEPE_W8PT_FORCE_110 | DFEPE_W8PT_NO_HARTLEY);
   A.row_per_pair = (flags & DFEPE_W8PT_ROW_PER_PAIR) != 0;
+  A.hartley = nullptr; A.hartley_mode = DFEPE_HARTLEY_NONE;  // dfepe_w8pt_fwd_shared sets them after this fill
   return A;
 }
 
@@ -533,11 +554,22 @@ struct W8Coop {
 // phase -- the stretch that holds the eigen solve and the rank-2 step, the kernel's register peak -- but fetched again (an L2 hit:
 // this very wavefront read them at its start) and re-derived by the same expressions: bit-identical outputs, ~120 more instructions,
 // 45 registers fewer.  (A register cap alone makes the compiler spill exactly these values to scratch memory and back.)
-template <int IT, bool RAW, bool PLAIN, int ROWS = 1, bool LEAN = false>
+// HM (the registers-resident row kernels, where csrc/fit_plan.h: fit_shares_hartley holds): what the instantiation does with the Hartley
+// record.  DFEPE_HARTLEY_NONE: nothing -- the code it was before the record existed.  H16_BY_LAUNCH: what the launch says
+// (A.hartley_mode, uniform over the launch) -- the ONE kernel the library builds per shape for the writer and its readers: a step
+// launches the writer once and readers L - 1 times, and a kernel that differs from the one before it starts with a cold
+// instruction cache (+1.4 us per launch at 4096 pairs, profiles/hartley_handover.md: as two kernels the hand-over LOST 2.8 us per
+// step).  DFEPE_HARTLEY_WRITE / DFEPE_HARTLEY_READ: that mode alone, for scripts/isa_phases.py, which counts what each mode issues:
+// writing stores the record behind phase 1 (+29 instructions, one store), reading loads it with the other loads and issues neither
+// the centroid pass nor phase 1 (-269 instructions, 17 of them fp64 seeds, +1 load at N = 100); by launch: both, 4 459 static.
+#define H16_BY_LAUNCH 3
+template <int IT, bool RAW, bool PLAIN, int ROWS = 1, bool LEAN = false, int HM = DFEPE_HARTLEY_NONE>
 __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair, double* xch, W8Coop* co = nullptr, const int rowid = 0) {
   static_assert(ROWS == 1 || (ROWS == 16 && IT > 0) || (ROWS == 2 && IT == 0),
                 "one row per pair, the 16 rows of a workgroup with the correspondences in registers, or two rows of one wavefront (looped)");
   static_assert(!LEAN || (IT > 0 && ROWS == 1), "the lean build is a variant of the registers-resident row kernel");
+  static_assert(HM == DFEPE_HARTLEY_NONE || (HM >= DFEPE_HARTLEY_WRITE && HM <= H16_BY_LAUNCH && IT > 0 && ROWS == 1),
+                "the Hartley record is written and read by the registers-resident row kernels only");
   constexpr int S = 16 * ROWS;  // lanes per pair
   const int l = rg_lane();
   const int L = rowid * 16 + l;  // lane within the pair
@@ -623,7 +655,21 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
       kept[it] = keep;
     });
   }
+  // Slot l & 7 of the pair's Hartley record: one 8-byte load per lane, unconditional (the launcher instantiates HM != 0 only with a
+  // record, so the address is valid for every lane; a writer loads what it is about to overwrite and drops it).  It is issued BEHIND
+  // the batch of match and weight loads, at the top of the block that follows it (the softmax, or what the plain weights leave of
+  // it): its address needs a pointer that is not among the preloaded SGPRs, and as a fifteenth load of the batch's own block it made
+  // the compiler split the batch into four dependent groups (loads, wait, decode, loads ...: the reading launch then took 11.4 us
+  // against the plain launch's 11.1 with 276 instructions fewer issued; here 10.5, profiles/hartley_handover.md).  The softmax hides its latency.
+  double hslot = 0.0;
+  auto hload = [&]() {
+    if constexpr (HM == DFEPE_HARTLEY_READ || HM == H16_BY_LAUNCH) hslot = A.hartley[mp * DFEPE_HARTLEY_DOUBLES + (size_t)(l & 7)];
+  };
+  if (!A.logits_mode) hload();
+  // reading or writing, uniform over the launch (a constant in every instantiation but H16_BY_LAUNCH)
+  const bool hread = HM == DFEPE_HARTLEY_READ || (HM == H16_BY_LAUNCH && A.hartley_mode == DFEPE_HARTLEY_READ);
   if (A.logits_mode) {
+    hload();
     // fused F.softmax(logits, dim=N) (DeepFNet.py:443,512)
     // the raw logit of correspondence `it` of this lane, -inf past the end
     auto logit_load = [&](int it) {
@@ -704,7 +750,16 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
   const bool hartley = (variant & DFEPE_W8PT_NO_HARTLEY) == 0;
   const double invN = 1.0 / (double)N;
   double c1x = 0.0, c1y = 0.0, c2x = 0.0, c2y = 0.0, s1 = 1.0, s2 = 1.0;
-  if (hartley) {
+  if (hread) {
+    // the six values as the writer held them behind its phase 1: six in-row broadcasts instead of the centroid pass and phase 1.
+    // The tag is checked without a branch: anything but a written record makes s1 NaN, and with it every output of the pair.
+    if (hartley) {
+      c1x = rg_bcast<H16_C1X>(hslot); c1y = rg_bcast<H16_C1Y>(hslot); s1 = rg_bcast<H16_S1>(hslot);
+      c2x = rg_bcast<H16_C2X>(hslot); c2y = rg_bcast<H16_C2Y>(hslot); s2 = rg_bcast<H16_S2>(hslot);
+      s1 = (rg_bcast<H16_TAG>(hslot) == H16_TAG_VALUE) ? s1 : __builtin_nan("");
+    }
+  DFEPE_MARK("P1");
+  } else if (hartley) {
     double sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0;
     float sme = 0.0f;
     for_points<IT>(nit, point_load, point, [&](int it, const PRec& r) {  // padding / dropped correspondences hold zeros
@@ -733,6 +788,15 @@ __device__ __forceinline__ void w8pt16_fwd_pair(const W8Args& A, const int pair,
     psumk(ds, 6);
     s1 = hscale * rcp_nr<2>(ds[0] * invN);
     s2 = hscale * rcp_nr<2>(ds[1] * invN);
+    if constexpr (HM == DFEPE_HARTLEY_WRITE || HM == H16_BY_LAUNCH) {
+      // write mode: lane l < 8 stores slot l of the record -- one select chain, one store per row; with several weight sets the
+      // first one writes (they share the correspondences, so the others hold the same values)
+      double mine = c1x;
+      mine = (l == H16_C1Y) ? c1y : mine; mine = (l == H16_S1) ? s1 : mine;
+      mine = (l == H16_C2X) ? c2x : mine; mine = (l == H16_C2Y) ? c2y : mine; mine = (l == H16_S2) ? s2 : mine;
+      mine = (l == 6) ? 0.0 : mine; mine = (l == H16_TAG) ? H16_TAG_VALUE : mine;
+      if (l < DFEPE_HARTLEY_DOUBLES && pair < A.Bm) A.hartley[mp * DFEPE_HARTLEY_DOUBLES + (size_t)l] = mine;
+    }
   }
 
   if (IT == 0 && A.logits_mode && !hartley) {

@@ -170,16 +170,23 @@ def _flags(raw: bool, logits: bool, row_per_pair: bool = False, extra: int = 0) 
 
 def w8pt_forward(pts1: Tensor, pts2: Optional[Tensor], weights: Tensor, raw: bool, image_w: float, image_h: float,
                  clamp_at: float, want_epi: bool, want_save: bool, logits: bool = False, F_out: Optional[Tensor] = None,
-                 row_per_pair: bool = False, extra_flags: int = 0, dst: Optional[dict] = None):
+                 row_per_pair: bool = False, extra_flags: int = 0, dst: Optional[dict] = None, hartley: Optional[tuple] = None):
     """Raw (non-differentiable) launch.  weights (or logits when ``logits``) [B,N].
     Returns F [B,3,3], residual [B,N], epi [B,N]|None, save|None, weights_out [B,N]|None.  ``F_out`` lets the caller
     provide the destination (e.g. one [B,3,3] slice of a per-layer stack).  ``row_per_pair`` forces one 16-lane row per pair
     where a cooperative workgroup per pair (N > 128 at small batch) would run: same function, same ``save`` record.
-    ``dst``: {"F" | "residual" | "epi" | "weights": (stack, l)} writes that output into row l of the caller's per-layer stack."""
+    ``dst``: {"F" | "residual" | "epi" | "weights": (stack, l)} writes that output into row l of the caller's per-layer stack.
+    ``hartley``: (buffer, mode) -- the Hartley record of dfepe_w8pt_fwd_shared (``hartley_record(B, device)``) and
+    _lib.HARTLEY_WRITE / HARTLEY_READ: a fit of the same correspondences, image size and Hartley flags as an earlier one on this
+    stream takes the transforms of Fit.normalize from it; the outputs are the same bit for bit."""
     L = _lib.lib()
     B, N = weights.shape
     dev = weights.device
     dst = dst or {}
+    hbuf, hmode = (None, _lib.HARTLEY_NONE) if hartley is None else hartley
+    if hbuf is not None and (hbuf.dtype != torch.float64 or hbuf.device != dev or not hbuf.is_contiguous() or
+                             hbuf.numel() < pts1.shape[0] * _lib.HARTLEY_DOUBLES):
+        raise ValueError(f"hartley buffer must be a contiguous float64 [{pts1.shape[0]}, {_lib.HARTLEY_DOUBLES}] tensor on {dev}")
 
     def out(name, shape, want=True):
         if not want:
@@ -197,10 +204,16 @@ def w8pt_forward(pts1: Tensor, pts2: Optional[Tensor], weights: Tensor, raw: boo
     save = torch.empty(B, L.dfepe_save_floats(), device=dev, dtype=torch.float32) if want_save else None
     w_out = out("weights", (B, N), logits)
     with _on(dev):
-        rc = L.dfepe_w8pt_fwd(_ptr(pts1), _ptr(pts2), _ptr(weights), B, N, 1, _flags(raw, logits, row_per_pair, extra_flags), float(image_w),
-                              float(image_h), float(clamp_at), _ptr(F), _ptr(residual), _ptr(epi), _ptr(save), _ptr(w_out), _stream())
-    _lib.check(rc, "dfepe_w8pt_fwd")
+        rc = L.dfepe_w8pt_fwd_shared(_ptr(pts1), _ptr(pts2), _ptr(weights), B, N, 1, _flags(raw, logits, row_per_pair, extra_flags),
+                                     float(image_w), float(image_h), float(clamp_at), _ptr(F), _ptr(residual), _ptr(epi), _ptr(save),
+                                     _ptr(w_out), _ptr(hbuf), int(hmode), _stream())
+    _lib.check(rc, "dfepe_w8pt_fwd_shared")
     return F, residual, epi, save, w_out
+
+
+def hartley_record(B: int, device) -> Tensor:
+    """A Hartley record for B pairs (w8pt_forward(hartley=...)): from the caching allocator, so a captured step owns it."""
+    return torch.empty(B, _lib.HARTLEY_DOUBLES, device=device, dtype=torch.float64)
 
 
 def w8pt_backward(pts1, pts2, weights, raw, image_w, image_h, clamp_at, save, F, gF, gRes, gEpi, logits=False, gW_extra=None,
@@ -270,10 +283,10 @@ def _cf(t: Optional[Tensor]) -> Optional[Tensor]:
 
 class _W8ptFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, pts1, pts2, weights, raw, image_w, image_h, clamp_at, want_epi, logits, extra_flags=0, dst=None):
+    def forward(ctx, pts1, pts2, weights, raw, image_w, image_h, clamp_at, want_epi, logits, extra_flags=0, dst=None, hartley=None):
         ctx.set_materialize_grads(False)  # unused outputs (e.g. the last layer's epi) must not cost a zero-fill
         F, residual, epi, save, w_out = w8pt_forward(pts1, pts2, weights, raw, image_w, image_h, clamp_at, want_epi,
-                                                     want_save=True, logits=logits, extra_flags=extra_flags, dst=dst)
+                                                     want_save=True, logits=logits, extra_flags=extra_flags, dst=dst, hartley=hartley)
         ctx.extra_flags = extra_flags
         ctx.save_for_backward(pts1, pts2 if pts2 is not None else pts1.new_empty(0), w_out if logits else weights, save, F)
         ctx.cfg = (raw, image_w, image_h, clamp_at, want_epi, logits)
@@ -292,15 +305,15 @@ class _W8ptFunction(torch.autograd.Function):
         gEpi = rest.pop(0) if want_epi else None
         gWout = rest.pop(0) if logits else None
         if gF is None and gRes is None and gEpi is None and gWout is None:
-            return (None,) * 11
+            return (None,) * 12
         want_pts = ctx.needs_input_grad[0] or (not raw and ctx.needs_input_grad[1])
         res = w8pt_backward(pts1, pts2 if pts2.numel() else None, weights, raw, image_w, image_h, clamp_at, save, F,
                             _cf(gF), _cf(gRes), _cf(gEpi), logits=logits, gW_extra=_cf(gWout), want_pts=want_pts,
                             extra_flags=ctx.extra_flags)
         if want_pts:
             gW, gP1, gP2 = res
-            return gP1, gP2, gW, None, None, None, None, None, None, None, None
-        return None, None, res, None, None, None, None, None, None, None, None
+            return gP1, gP2, gW, None, None, None, None, None, None, None, None, None
+        return None, None, res, None, None, None, None, None, None, None, None, None
 
 
 def w8pt(pts1: Tensor, pts2: Tensor, weights: Tensor, clamp_at: float = 0.5, want_epi: bool = False, normalize_rows: bool = True):
@@ -318,23 +331,24 @@ def w8pt(pts1: Tensor, pts2: Tensor, weights: Tensor, clamp_at: float = 0.5, wan
 
 
 def w8pt_raw(matches: Tensor, weights: Tensor, image_w: float, image_h: float, clamp_at: float = 0.5,
-             want_epi: bool = True):
-    """Differentiable fit straight from pixel matches [B,N,4] (image-size normalisation fused)."""
+             want_epi: bool = True, hartley: Optional[tuple] = None):
+    """Differentiable fit straight from pixel matches [B,N,4] (image-size normalisation fused).  ``hartley``: see w8pt_forward."""
     m = _prep(matches, "matches")
     w = _prep(weights.reshape(weights.shape[0], -1), "weights")
     _shape(m, "matches (pixel x1,y1,x2,y2)", w.shape[0], w.shape[1], 4)
-    return _W8ptFunction.apply(m, None, w, True, float(image_w), float(image_h), clamp_at, want_epi, False)
+    return _W8ptFunction.apply(m, None, w, True, float(image_w), float(image_h), clamp_at, want_epi, False, 0, None, hartley)
 
 
 def w8pt_raw_logits(matches: Tensor, logits: Tensor, image_w: float, image_h: float, clamp_at: float = 0.5,
-                    want_epi: bool = True, dst: Optional[dict] = None):
+                    want_epi: bool = True, dst: Optional[dict] = None, hartley: Optional[tuple] = None):
     """As w8pt_raw but takes the estimator's logits and fuses F.softmax(dim=N); additionally returns the weights
     (differentiable: the next estimator layer consumes them).  Returns (F, residual[, epi], weights).
-    ``dst`` (see w8pt_forward): rows of the caller's per-layer stacks to write the outputs into."""
+    ``dst`` (see w8pt_forward): rows of the caller's per-layer stacks to write the outputs into.
+    ``hartley`` (see w8pt_forward): (record, mode), for a model that fits the same matches at every layer."""
     m = _prep(matches, "matches")
     l = _prep(logits.reshape(logits.shape[0], -1), "logits")
     _shape(m, "matches (pixel x1,y1,x2,y2)", l.shape[0], l.shape[1], 4)
-    return _W8ptFunction.apply(m, None, l, True, float(image_w), float(image_h), clamp_at, want_epi, True, 0, dst)
+    return _W8ptFunction.apply(m, None, l, True, float(image_w), float(image_h), clamp_at, want_epi, True, 0, dst, hartley)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -78,7 +78,7 @@ class _HotPathFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, matches, logits_layers, Ks, virt1, virt2, q_gt, t_gt, R_gt, hw_T, cfg):
-        (H, W, clamp_at, qt, clamp_q, clamp_t, balance_q, balance_t, batched, balance_F, fused_tail, grad_pairs, defer_head, exchange) = cfg
+        (H, W, clamp_at, qt, clamp_q, clamp_t, balance_q, balance_t, batched, balance_F, fused_tail, grad_pairs, defer_head, exchange, share_hartley) = cfg
         ctx.set_materialize_grads(False)  # 13 auxiliary outputs: do not let autograd zero-fill [L,B,N] gradients for them
         lib = _lib.lib()
         L, B, N = logits_layers.shape
@@ -102,11 +102,17 @@ class _HotPathFunction(torch.autograd.Function):
                                         weights.data_ptr(), st)
                 _lib.check(rc, "dfepe_w8pt_fwd")
             else:
+                # every layer fits the SAME matches, and Fit.normalize is unweighted: layer 0 writes its Hartley transforms into
+                # a record, layers 1..L-1 read them instead of computing them again (bit-identical outputs).  One buffer per call
+                # from the caching allocator, so that a captured step owns it.
+                share = share_hartley and L > 1 and lib.dfepe_w8pt_shares_hartley(N, flags) == 1
+                hartley = torch.empty(B, _lib.HARTLEY_DOUBLES, device=dev, dtype=torch.float64) if share else None
                 for l in range(L):
-                    rc = lib.dfepe_w8pt_fwd(matches.data_ptr(), None, logits_layers[l].data_ptr(), B, N, 1, flags, W, H, 0.5,
-                                            F_layers[l].data_ptr(), residuals[l].data_ptr(), epis[l].data_ptr(),
-                                            saves[l].data_ptr(), weights[l].data_ptr(), st)
-                    _lib.check(rc, "dfepe_w8pt_fwd")
+                    mode = _lib.HARTLEY_NONE if not share else (_lib.HARTLEY_WRITE if l == 0 else _lib.HARTLEY_READ)
+                    rc = lib.dfepe_w8pt_fwd_shared(matches.data_ptr(), None, logits_layers[l].data_ptr(), B, N, 1, flags, W, H, 0.5,
+                                                   F_layers[l].data_ptr(), residuals[l].data_ptr(), epis[l].data_ptr(),
+                                                   saves[l].data_ptr(), weights[l].data_ptr(), ops._ptr(hartley), mode, st)
+                    _lib.check(rc, "dfepe_w8pt_fwd_shared")
             loss_sum = torch.empty(L, B, device=dev)
             E_layers = torch.empty(L, B, 3, 3, device=dev)
             q_l2 = t_l2 = R_deg = t_deg = sel = None
@@ -187,7 +193,7 @@ class _HotPathFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, *unused):
         matches, weights, Ks, virt1, virt2, q_gt, t_gt, hw_T, F_layers, E_layers, saves = ctx.saved_tensors[:11]
-        (H, W, clamp_at, qt, clamp_q, clamp_t, balance_q, balance_t, batched, balance_F, _ft, grad_pairs, _dh, _ex) = ctx.cfg
+        (H, W, clamp_at, qt, clamp_q, clamp_t, balance_q, balance_t, batched, balance_F, _ft, grad_pairs, _dh, _ex, _sh) = ctx.cfg
         lib = _lib.lib()
         L, B, N = weights.shape
         M = virt1.shape[1]
@@ -247,7 +253,8 @@ def hot_path_fused(matches: Tensor, logits_layers: Tensor, Ks: Tensor, virt1: Te
                    clamp_q: float = 0.1, clamp_t: float = 0.5, balance_q: float = 1.0, balance_t: float = 0.1,
                    hw_T: Optional[Tensor] = None, layers_batched: bool = False, balance_F: float = 1.0, fused_tail: bool = True,
                    grad_pairs: Optional[int] = None, defer_loss_head: bool = False, loss_exchange=None,
-                   exchange_branch: bool = False, exchange_stream: Optional["torch.cuda.Stream"] = None) -> Dict[str, Tensor]:
+                   exchange_branch: bool = False, exchange_stream: Optional["torch.cuda.Stream"] = None,
+                   share_hartley: bool = True) -> Dict[str, Tensor]:
     """Same contract and same numbers as hot_path_forward, 12 kernel launches instead of ~120:
     loss = balance_F * loss_F + loss_qt.  The reference's pipeline drops the F-loss from the objective when if_qt_loss
     (Train_model_pipeline.py:580-587, `loss += loss_F * balance_F` commented out): that is balance_F = 0; the solver-only
@@ -267,7 +274,10 @@ def hot_path_fused(matches: Tensor, logits_layers: Tensor, Ks: Tensor, virt1: Te
     tail -> [head -> all_reduce] || [L x w8pt_bwd].  Measured on this stack (scripts/exchange_probe.py, one-rank RCCL, B = 4096):
     the in-order node costs nothing measurable, the branch +33 us per step (cross-stream edges of a hipGraph, like stream-event
     waits outside one, cost 18-30 us each here -- more than the 72-byte collective they would hide), so the branch is the option,
-    not the default.  Either way ``packed`` holds the reduced sums after the backward."""
+    not the default.  Either way ``packed`` holds the reduced sums after the backward.
+    ``share_hartley``: the per-layer fits take the Hartley transforms of Fit.normalize from the first layer's fit (they depend on
+    the matches alone; dfepe_w8pt_fwd_shared) -- the same numbers bit for bit; ``False`` computes them in every launch.  Without
+    effect on ``layers_batched`` and for N > 128."""
     L, B, N = logits_layers.shape
     H, W = float(image_size[0]), float(image_size[1])
     dev = matches.device
@@ -280,7 +290,7 @@ def hot_path_fused(matches: Tensor, logits_layers: Tensor, Ks: Tensor, virt1: Te
             raise _lib.DfepeError("loss_exchange rides behind the fused loss tail (fused_tail=True)")
         exchange = (loss_exchange, (exchange_stream if exchange_stream is not None else _exchange_stream(dev)) if exchange_branch else None)
     cfg = (H, W, float(clamp_at), bool(qt), float(clamp_q), float(clamp_t), float(balance_q), float(balance_t), bool(layers_batched),
-           float(balance_F), bool(fused_tail), grad_pairs, bool(defer_loss_head), exchange)
+           float(balance_F), bool(fused_tail), grad_pairs, bool(defer_loss_head), exchange, bool(share_hartley))
     res = _HotPathFunction.apply(f32(matches), f32(logits_layers), f32(Ks), f32(virt1), f32(virt2), f32(q_gt.reshape(B, 4)),
                                  f32(t_gt.reshape(B, 3)), f32(R_gt.reshape(B, 3, 3)), f32(hw_T), cfg)
     loss, F_layers, residuals, epis, weights, E_layers, loss_sum, packed, scalars = res[:9]

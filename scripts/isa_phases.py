@@ -1,5 +1,6 @@
 """Per-phase static instruction counts of the row-per-pair forward/backward kernels.
-   python scripts/isa_phases.py fwd|bwd [IT] [RAW]     (compiles one instantiation with -DDFEPE_ISA_MARKS to assembly)"""
+   python scripts/isa_phases.py fwd|bwd [IT] [RAW] [HM]     (compiles one instantiation with -DDFEPE_ISA_MARKS to assembly;
+   HM, forward only: 0 no Hartley record (default), 1 the launch that writes it, 2 a launch that reads it)"""
 import collections
 import os
 import re
@@ -18,7 +19,7 @@ __global__ void __launch_bounds__(256) k(const W8Args A) {
   const int row = (int)(threadIdx.x >> 4);
   const int pair = (int)blockIdx.x * 16 + row;
   if (pair >= A.B) return;
-  w8pt16_fwd_pair<%d, %s, true>(A, pair, xch + row * 36);
+  w8pt16_fwd_pair<%d, %s, true, 1, false, %d>(A, pair, xch + row * 36);
 }
 """,
     "bwd": """#include "dfepe_common.h"
@@ -39,7 +40,8 @@ def main():
     raw = sys.argv[3] if len(sys.argv) > 3 else "true"
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "one.hip")
-        open(src, "w").write(SRC[which] % (it, raw))
+        hm = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+        open(src, "w").write(SRC[which] % ((it, raw, hm) if which == "fwd" else (it, raw)))
         out = os.path.join(d, "one.s")
         subprocess.run(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fno-fast-math", "-ffp-contract=on", "-DDFEPE_ISA_MARKS", *os.environ.get("DFEPE_EXTRA_DEFS", "").split(),
                         f"-I{REPO}/include", f"-I{CSRC}", "-S", "--cuda-device-only", src, "-o", out,
