@@ -1151,6 +1151,90 @@ int dfepe_average_precision(const unsigned char *labels, const double *scores, c
                             int *tp_at, int *cnt_at, void *stream);
 int dfepe_matching_score(const int *n_inliers, const int *n_kp1, const int *n_unwarped, int B, double *mscore, void *stream);
 
+/*
+ * The SuperPoint output processing of the end-to-end training path: process_SP_output (deepFEPE/train_good_utils.py:727-755),
+ * batched over B images.  Its steps are methods of the superpoint package (superpoint.models.model_utils.SuperPointNet_process,
+ * superpoint.utils), which the reference's tree does not hold: what follows is the published algorithm, unpinned, and this text
+ * is its specification.  Data are fp32, the arithmetic of every value is fp64 and is rounded once.  No atomics; every cell has one
+ * writer and every sum a fixed order, so two calls on the same input are bit-identical; no host synchronisation, no allocation;
+ * all refusals are made before anything is launched, in the order in which they are listed.  H, W: the image in pixels; a cell is
+ * 8 x 8 pixels, (Hc, Wc) = (H/8, W/8).  Limits: H * W <= 2^24 pixels per image, patch_size <= 63; beyond: UNSUPPORTED.
+ *
+ * dfepe_sp_flatten: flattenDetection after set_nan2zero (train_good_utils.py:741-743, models/model_utils.py:5-15).
+ *   semi [B,65,Hc,Wc]; a NaN is read as 0.  heatmap [B,1,H,W] (16-byte aligned): the softmax over the 65 channels without channel
+ *   64 (the dustbin); channel c of cell (hc, wc) is pixel (8 hc + c/8, 8 wc + c%8).
+ *   Refused: B < 0, H or W < 1 or not a multiple of 8: INVALID_ARG.  H * W beyond the limit: UNSUPPORTED.  Then B == 0 returns OK.
+ *   A null semi, a null or misaligned heatmap: INVALID_ARG.
+ * dfepe_sp_flatten_bwd: its adjoint.  g_heatmap [B,1,H,W] -> g_semi [B,65,Hc,Wc], all 65 channels written:
+ *   g_semi[c] = p_c (g_c - sum_{k<64} g_k p_k) with g_64 = 0, so the dustbin receives its share through the normaliser; 0 where
+ *   semi is NaN (the 0 it was read as is a constant).  Refusals as above (null semi, g_heatmap or g_semi: INVALID_ARG).
+ *
+ * dfepe_sp_nms: heatmap_to_nms (train_good_utils.py:745), the greedy nms_fast, for any input.
+ *   heatmap [B,1,H,W]; candidates are the pixels with h >= conf_thresh (a NaN is none).  nms_dist = d >= 0, border_remove = r >= 0.
+ *   Candidates are visited by confidence descending and, among equal confidences, row-major index ascending (a stated rule: the
+ *   reference's argsort is not stable).  A candidate is kept iff no candidate kept before it lies within Chebyshev distance d.
+ *   After that a kept point with x < r, x >= W - r, y < r or y >= H - r is removed: it has still suppressed its neighbours.
+ *   nms_map [B,1,H,W]: 1.0 at the kept points, 0.0 elsewhere (heatmap_to_nms(tensor=True)).  cap = dfepe_sp_nms_capacity(H, W, d) =
+ *   ceil(H/(d+1)) ceil(W/(d+1)) (0 for arguments that dfepe_sp_nms refuses): two kept points never share a (d+1) x (d+1) block, so
+ *   the list cannot overflow, and a constant heatmap reaches cap.  pts [B,cap,2] int32 (x, y) in row-major order of the pixels
+ *   (the order of nonzero()), conf [B,cap] their heat, count [B] int32; entries from count[b] on are 0.
+ *   workspace: dfepe_sp_nms_workspace_bytes(B, H, W) bytes of device memory, overwritten: 0 (NULL allowed) up to H * W = 12288
+ *   pixels, where heat and state stay in LDS, else five bytes per pixel (a state byte, the B planes together rounded up to 16,
+ *   then an int32 list of the pixels still undecided when the one-workgroup loop takes over).
+ *   Refused: B < 0, H or W < 1, d < 0, r < 0: INVALID_ARG.  Then B == 0 returns OK.  H * W beyond the limit or B > 65535:
+ *   UNSUPPORTED.  A null heatmap, nms_map, pts, conf or count, a null workspace where one is needed: INVALID_ARG.
+ *   The loop runs on the device as a fixpoint without a round limit: every candidate starts undecided; an undecided candidate
+ *   becomes suppressed when a kept candidate that outranks it lies in its window, kept when every candidate in its window that
+ *   outranks it is suppressed; it ends when none is undecided (DESIGN.md 3.15 shows that this is the greedy loop's result).
+ *   One workgroup per image loops on a workgroup-wide test; above the LDS size four rounds over the whole device come first.
+ *
+ * dfepe_sp_soft_argmax: pred_soft_argmax (train_good_utils.py:747).
+ *   pts, count: a point list as dfepe_sp_nms writes it (image b uses its first clamp(count[b], 0, cap) rows).  patch_size = p, odd,
+ *   1 <= p <= 2 border_remove + 1, so that the p x p patch h centred on a listed point lies inside the image (a row whose patch
+ *   does not is treated as not listed).  q = h / (sum h + 1e-6); q < 0 -> 1e-6; l = log q; e = exp(l - max l);
+ *   off_x = sum x e / (sum e + 1e-6) - p/2 (integer division) with x = 0..p-1 the column, off_y alike with the row.  A patch with
+ *   sum h <= 0 gives (0, 0) and no gradient (a stated rule: the formulas give NaN).  pred [B,cap,2] (x, y), 0 for rows not listed;
+ *   patches [B,cap,p,p] or NULL: q after the clamp.
+ *   Refused: B < 0, H or W < 1, cap < 0, r < 0, p < 1, p even, p > 2r + 1: INVALID_ARG.  H * W beyond the limit, p > 63 or B * cap >=
+ *   2^31: UNSUPPORTED.  Then B == 0 or cap == 0 returns OK.  A null heatmap, pts, count or pred: INVALID_ARG.
+ * dfepe_sp_soft_argmax_bwd: g_pred [B,cap,2] -> g_heatmap [B,1,H,W], written whole.  The exact derivative of the formulas above,
+ *   the maximum's share included and spread evenly over the entries that attain it; nothing flows through a clamped entry.  In
+ *   gather form: each pixel sums, in row-major window order, what the listed points whose patch covers it send, so overlapping
+ *   patches (p > d) are bit-identical from run to run.  workspace: dfepe_sp_soft_argmax_bwd_workspace_bytes(B, H, W, cap) bytes,
+ *   16-byte aligned, overwritten (a dense int32 map of list positions and one record per listed point).
+ *   Refusals as the forward's; then B == 0 returns OK; a null heatmap or g_heatmap, a null or misaligned workspace, with cap > 0 a
+ *   null pts, count or g_pred: INVALID_ARG.
+ *
+ * dfepe_sp_sample_desc: sample_desc_from_points (train_good_utils.py:750, inside batch_extract_features).
+ *   desc [B,D,Hc,Wc]; positions pts + pred in pixels (pred NULL: pts alone).  Normalised coordinates x / (W/2) - 1, y / (H/2) - 1;
+ *   bilinear sampling with zero padding, grid_sample's rule for align_corners (1 is what the torch version that the reference pins,
+ *   1.3.1, did; 0 is today's default); the sample is divided by its L2 norm over D, a zero norm gives zeros (a stated rule).
+ *   out [B,cap,D], zero rows from count[b] on.  Forward only: the reference detaches these descriptors (train_good_utils.py:664).
+ *   Refused: B < 0, D < 1, H or W < 1 or not a multiple of 8, cap < 0, align_corners not 0 or 1: INVALID_ARG.  Then B == 0 or cap == 0
+ *   returns OK.  H * W beyond the limit or B > 65535: UNSUPPORTED.  A null desc, pts, count or out: INVALID_ARG.
+ *
+ * dfepe_gather_offsets_bwd: the adjoint of the offsets output of dfepe_gather_matches (train_good_utils.py:700-711) into off1 and
+ *   off2.  g_offsets [B,n_out,4] -> g_off1 [B,N1,2], g_off2 [B,N2,2], written whole.  Padding repeats choices, so rows collide: one
+ *   lane per source keypoint adds the rows that name it in ascending row order, in fp64.
+ *   Refused: B < 0, N1 or N2 < 1, n_out < 0: INVALID_ARG.  Then B == 0 returns OK.  B > 65535: UNSUPPORTED.  A null g_off1, g_off2,
+ *   m_idx1 or m_idx2, with n_out > 0 a null g_offsets or choice: INVALID_ARG.
+ */
+int dfepe_sp_nms_capacity(int H, int W, int nms_dist);
+size_t dfepe_sp_nms_workspace_bytes(int B, int H, int W);
+size_t dfepe_sp_soft_argmax_bwd_workspace_bytes(int B, int H, int W, int cap);
+int dfepe_sp_flatten(const float *semi, int B, int H, int W, float *heatmap, void *stream);
+int dfepe_sp_flatten_bwd(const float *semi, const float *g_heatmap, int B, int H, int W, float *g_semi, void *stream);
+int dfepe_sp_nms(const float *heatmap, int B, int H, int W, float conf_thresh, int nms_dist, int border_remove, void *workspace,
+                 float *nms_map, int *pts, float *conf, int *count, void *stream);
+int dfepe_sp_soft_argmax(const float *heatmap, const int *pts, const int *count, int B, int H, int W, int cap, int patch_size,
+                         int border_remove, float *pred, float *patches, void *stream);
+int dfepe_sp_soft_argmax_bwd(const float *heatmap, const int *pts, const int *count, const float *g_pred, int B, int H, int W, int cap,
+                             int patch_size, int border_remove, void *workspace, float *g_heatmap, void *stream);
+int dfepe_sp_sample_desc(const float *desc, const int *pts, const float *pred, const int *count, int B, int D, int H, int W, int cap,
+                         int align_corners, float *out, void *stream);
+int dfepe_gather_offsets_bwd(const float *g_offsets, int B, int N1, int N2, const int *m_idx1, const int *m_idx2, const int *choice,
+                             int n_out, float *g_off1, float *g_off2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ HOMOGRAPHY_ALL_POINTS = 1  # dfepe_ransac_homography: cv2's method = 0 (DFEPE_HO
 HOMOGRAPHY_NO_REFINE = 2  # ... no Levenberg-Marquardt step (DFEPE_HOMOGRAPHY_NO_REFINE)
 HOMOGRAPHY_MAX_N = 4096
 DETECTOR_EVAL_MAX_N = 4096  # dfepe_keypoint_repeatability (points per image), dfepe_average_precision (entries per pair): de::kMaxN
+SP_MAX_PIXELS = 1 << 24  # dfepe_sp_*: pixels per image (sp::kMaxPixels, csrc/sp_process_math.h)
+SP_LDS_PIXELS = 12288  # dfepe_sp_nms: pixels per image up to which no workspace is needed (sp::kLdsPixels)
+SP_MAX_PATCH = 63  # dfepe_sp_soft_argmax: largest patch_size (sp::kMaxPatch)
 
 _P = c_void_p
 _SIGNATURES = {
@@ -144,6 +147,16 @@ _SIGNATURES = {
                                              _P, _P, _P, _P]),
     "dfepe_average_precision": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     "dfepe_matching_score": (c_int, [_P, _P, _P, c_int, _P, _P]),
+    "dfepe_sp_nms_capacity": (c_int, [c_int, c_int, c_int]),
+    "dfepe_sp_nms_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_sp_soft_argmax_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dfepe_sp_flatten": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "dfepe_sp_flatten_bwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "dfepe_sp_nms": (c_int, [_P, c_int, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "dfepe_sp_soft_argmax": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "dfepe_sp_soft_argmax_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "dfepe_sp_sample_desc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "dfepe_gather_offsets_bwd": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

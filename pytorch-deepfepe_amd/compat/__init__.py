@@ -19,6 +19,8 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.dsac_tools.utils_vis       ->   compat.utils_vis       (reproj_and_scatter without the drawing)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)
+    superpoint.models.model_utils,      ->   compat.superpoint_process (flattenDetection, SuperPointNet_process: what
+    superpoint.utils.utils                                          process_SP_output calls; the network stays the caller's)
     deepFEPE.utils.eval_tools           ->   compat.eval_tools      (Exp_table_processor's odometry methods: get_abs_poses,
                                                                     compensate_poses, compute_pose_error, pose_seq_ate; plus
                                                                     relative_pose_cam_to_body and the on-device odometry_summary)
@@ -27,7 +29,7 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, model_wrap, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
+from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401
 from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
 from .detector_evaluation import compute_repeatability, compute_repeatability_batch  # noqa: F401

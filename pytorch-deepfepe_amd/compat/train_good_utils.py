@@ -618,10 +618,28 @@ def matches_from_SP_outputs(xs_SP, deses_SP, reses_SP, nn_thresh, out_num_points
             "xs_SP": xs_all}
 
 
+def process_SP_output(output, sp_processer):
+    """train_good_utils.py:727-755 with ``sp_processer`` a compat.superpoint_process.SuperPointNet_process: heatmap, NMS,
+    sub-pixel offsets, points and descriptors of the whole batch in five launches.  ``output`` (the network's dict with
+    'semi' [B,65,Hc,Wc] and 'desc' [B,D,Hc,Wc]) gains 'pts_int' [B,N,2] (no grad), 'pts_offset' [B,N,2] (grad, back to semi)
+    and 'pts_desc' [B,N,D] (detached: the matcher receives them through .detach() in the reference too, :664).  NaNs in semi and
+    desc are read as 0 inside the kernels (set_nan2zero, :741-742); the network's tensors are not written to."""
+    from .superpoint_process import flattenDetection
+
+    semi, desc = output["semi"], output["desc"]
+    heatmap = flattenDetection(semi)  # [batch_size, 1, H, W]
+    heatmap_nms_batch = sp_processer.heatmap_to_nms(heatmap, tensor=True)
+    residual = sp_processer.pred_soft_argmax(heatmap_nms_batch, heatmap)["pred"]
+    outs = sp_processer.batch_extract_features(desc, heatmap_nms_batch, residual)
+    output.update(outs)
+    return output
+
+
 def get_matches_from_SP(imgs_grey, net_SP, SP_processer, SP_tracker, out_num_points=1000, process_SP_output=None):
-    """Same call as the reference's get_matches_from_SP (train_good_utils.py:649-724).  The SuperPoint front-end stays
+    """Same call as the reference's get_matches_from_SP (train_good_utils.py:649-724).  The SuperPoint network stays
     the caller's: ``net_SP`` and ``process_SP_output`` (by default the reference's own, importable when this runs inside
-    the reference tree, :665) produce keypoints / descriptors / offsets; the matching, crop/pad and gather of all pairs
+    the reference tree, :665; pass this module's ``process_SP_output`` with a compat.superpoint_process.SuperPointNet_process for
+    the one built here) produce keypoints / descriptors / offsets; the matching, crop/pad and gather of all pairs
     then run as two launches instead of a per-pair numpy loop.  ``SP_tracker`` only supplies ``nn_thresh``."""
     if process_SP_output is None:
         from train_good_utils import process_SP_output  # the reference's module (superpoint front-end, out of scope here)

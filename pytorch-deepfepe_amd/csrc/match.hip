@@ -258,6 +258,42 @@ gather_matches_kernel(const float* __restrict__ pts1, const float* __restrict__ 
   if (quality != nullptr) quality[t] = score[b * N1 + c];
 }
 
+// The adjoint of the offsets output of gather_matches_kernel: row t of g_offsets belongs to keypoint m_idx1[choice[t]] of image 1
+// (its first two columns) and m_idx2[choice[t]] of image 2 (the last two).  Padding repeats choices, so rows collide: one lane per
+// source keypoint (blockIdx.z: the image) walks the n_out rows in ascending order, their sources staged in LDS in tiles, and adds
+// its own in fp64 -- no atomics, one writer per cell, the same bits on every run.
+constexpr int kGatherTile = 1024;
+__global__ void __launch_bounds__(256)
+gather_offsets_bwd_kernel(const float* __restrict__ g_offsets, int N1, int N2, const int* __restrict__ m_idx1,
+                          const int* __restrict__ m_idx2, const int* __restrict__ choice, int n_out, float* __restrict__ g_off1,
+                          float* __restrict__ g_off2) {
+  __shared__ int src[kGatherTile];
+  const size_t b = blockIdx.y;
+  const int second = blockIdx.z, tid = threadIdx.x;
+  const int N = second ? N2 : N1;
+  if ((int)(blockIdx.x * 256) >= N) return;  // uniform over the workgroup, before any barrier
+  const int i = blockIdx.x * 256 + tid;
+  const int* m = (second ? m_idx2 : m_idx1) + b * N1;
+  const float* g = g_offsets + b * (size_t)n_out * 4 + (second ? 2 : 0);
+  double ax = 0.0, ay = 0.0;
+  for (int t0 = 0; t0 < n_out; t0 += kGatherTile) {
+    const int cnt = (n_out - t0 < kGatherTile) ? n_out - t0 : kGatherTile;
+    __syncthreads();
+    for (int j = tid; j < cnt; j += 256) {
+      const int c = choice[b * n_out + t0 + j];
+      src[j] = (c >= 0 && c < N1) ? m[c] : -1;
+    }
+    __syncthreads();
+    for (int j = 0; j < cnt; ++j) {
+      if (src[j] == i) {  // every lane reads the same cell: a broadcast
+        ax += (double)g[(size_t)(t0 + j) * 4];
+        ay += (double)g[(size_t)(t0 + j) * 4 + 1];
+      }
+    }
+  }
+  if (i < N) reinterpret_cast<float2*>(second ? g_off2 : g_off1)[b * N + i] = make_float2((float)ax, (float)ay);
+}
+
 }  // namespace
 
 extern "C" size_t dfepe_nn_match_workspace_bytes(int B, int N1, int N2) {
@@ -301,5 +337,18 @@ extern "C" int dfepe_gather_matches(const float* pts1, const float* pts2, const 
   const size_t n = (size_t)B * n_out;
   hipLaunchKernelGGL(gather_matches_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      pts1, pts2, off1, off2, B, N1, N2, m_idx1, m_idx2, score, choice, n_out, xs, offsets, quality);
+  return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
+}
+
+extern "C" int dfepe_gather_offsets_bwd(const float* g_offsets, int B, int N1, int N2, const int* m_idx1, const int* m_idx2,
+                                        const int* choice, int n_out, float* g_off1, float* g_off2, void* stream) {
+  if (B < 0 || N1 <= 0 || N2 <= 0 || n_out < 0) return DFEPE_ERR_INVALID_ARG;
+  if (B == 0) return DFEPE_OK;
+  if (B > 65535) return DFEPE_ERR_UNSUPPORTED;
+  if (!g_off1 || !g_off2 || !m_idx1 || !m_idx2) return DFEPE_ERR_INVALID_ARG;
+  if (n_out > 0 && (!g_offsets || !choice)) return DFEPE_ERR_INVALID_ARG;
+  const int nmax = N1 > N2 ? N1 : N2;
+  hipLaunchKernelGGL(gather_offsets_bwd_kernel, dim3((unsigned)((nmax + 255) / 256), B, 2), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), g_offsets, N1, N2, m_idx1, m_idx2, choice, n_out, g_off1, g_off2);
   return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
 }

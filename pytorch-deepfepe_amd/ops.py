@@ -1584,16 +1584,53 @@ def knn_match(desc1: Tensor, desc2: Tensor, ratio: float = 0.8, ratio_test: bool
     return nn1, nn2, dist1, dist2, m1, m2, sc, cnt
 
 
+class _GatherOffsetsFunction(torch.autograd.Function):
+    """gather_matches with the offsets attached to off1 / off2: the same launch, and dfepe_gather_offsets_bwd on the way back."""
+
+    @staticmethod
+    def forward(ctx, o1, o2, p1, p2, m_idx1, m_idx2, score, choice):
+        xs, offs, q = _gather_launch(p1, p2, o1, o2, m_idx1, m_idx2, score, choice)
+        ctx.save_for_backward(m_idx1, m_idx2, choice)
+        ctx.sizes = (p1.shape[0], p1.shape[1], p2.shape[1])
+        ctx.mark_non_differentiable(xs, q)
+        return xs, offs, q
+
+    @staticmethod
+    def backward(ctx, _gx, g_offs, _gq):
+        m_idx1, m_idx2, choice = ctx.saved_tensors
+        B, N1, N2 = ctx.sizes
+        g = g_offs.contiguous().float()
+        g1 = torch.empty(B, N1, 2, device=g.device, dtype=torch.float32)
+        g2 = torch.empty(B, N2, 2, device=g.device, dtype=torch.float32)
+        with _on(g.device):
+            rc = _lib.lib().dfepe_gather_offsets_bwd(_ptr(g), B, N1, N2, _ptr(m_idx1), _ptr(m_idx2), _ptr(choice), choice.shape[1], _ptr(g1),
+                                                     _ptr(g2), _stream())
+        _lib.check(rc, "dfepe_gather_offsets_bwd")
+        return g1, g2, None, None, None, None, None, None
+
+
 def gather_matches(pts1: Tensor, pts2: Tensor, off1: Optional[Tensor], off2: Optional[Tensor], m_idx1: Tensor, m_idx2: Tensor,
                    score: Tensor, choice: Tensor):
     """choice [B,n_out] int32 positions into each pair's match list -> xs [B,n_out,4], offsets [B,n_out,4] | None,
-    quality [B,n_out,1]  (train_good_utils.py:698-716)."""
+    quality [B,n_out,1]  (train_good_utils.py:698-716).  Where off1 or off2 requires a gradient, offsets carries it back to them
+    (rows that name the same keypoint are added in ascending row order); xs and quality carry none."""
     p1, p2 = _prep(pts1, "pts1"), _prep(pts2, "pts2")
     B, N1, N2 = p1.shape[0], p1.shape[1], p2.shape[1]
     o1 = None if off1 is None else _prep(off1, "off1")
     o2 = None if off2 is None else _prep(off2, "off2")
     if m_idx1.shape != (B, N1) or m_idx1.dtype != torch.int32 or choice.dtype != torch.int32 or not choice.is_contiguous():
         raise ValueError("m_idx1/m_idx2 must be the [B,N1] int32 outputs of nn_match_two_way and choice a contiguous int32 [B,n_out]")
+    if o1 is not None and o2 is not None and torch.is_grad_enabled() and (o1.requires_grad or o2.requires_grad):
+        _shape(o1, "off1", B, N1, 2)
+        _shape(o2, "off2", B, N2, 2)
+        if m_idx2.shape != (B, N1) or m_idx2.dtype != torch.int32:
+            raise ValueError("m_idx2 must be the [B,N1] int32 output of nn_match_two_way")
+        return _GatherOffsetsFunction.apply(o1, o2, p1.detach(), p2.detach(), m_idx1.contiguous(), m_idx2.contiguous(), score, choice)
+    return _gather_launch(p1, p2, o1, o2, m_idx1, m_idx2, score, choice)
+
+
+def _gather_launch(p1, p2, o1, o2, m_idx1, m_idx2, score, choice):
+    B, N1, N2 = p1.shape[0], p1.shape[1], p2.shape[1]
     n_out = choice.shape[1]
     dev = p1.device
     xs = torch.empty(B, n_out, 4, device=dev)
@@ -1800,4 +1837,174 @@ def matching_score(n_inliers: Tensor, n_kp1: Tensor, n_unwarped: Tensor) -> Tens
     with _on(dev):
         rc = _lib.lib().dfepe_matching_score(_ptr(args[0]), _ptr(args[1]), _ptr(args[2]), B, _ptr(out), _stream())
     _lib.check(rc, "dfepe_matching_score")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# SuperPoint output processing (process_SP_output, train_good_utils.py:727-755): heatmap, NMS, soft-argmax, descriptors
+# ------------------------------------------------------------------------------------------------
+def _sp_pixels(H: int, W: int, what: str) -> None:
+    if H * W > _lib.SP_MAX_PIXELS:
+        raise _lib.DfepeError(f"{what}: {H}x{W} pixels per image; at most {_lib.SP_MAX_PIXELS}")
+
+
+def _sp_bytes(n: int, dev) -> Tensor:
+    """n bytes of 16-byte aligned device memory (at least one cell)."""
+    return torch.empty(max(1, (int(n) + 15) // 16), 2, dtype=torch.float64, device=dev)
+
+
+class _SpFlattenFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, semi):
+        B, _, Hc, Wc = semi.shape
+        heat = torch.empty(B, 1, 8 * Hc, 8 * Wc, device=semi.device, dtype=torch.float32)
+        with _on(semi.device):
+            rc = _lib.lib().dfepe_sp_flatten(_ptr(semi), B, 8 * Hc, 8 * Wc, _ptr(heat), _stream())
+        _lib.check(rc, "dfepe_sp_flatten")
+        ctx.save_for_backward(semi)
+        return heat
+
+    @staticmethod
+    def backward(ctx, g):
+        (semi,) = ctx.saved_tensors
+        B, _, Hc, Wc = semi.shape
+        g = g.contiguous().float()
+        g_semi = torch.empty_like(semi)
+        with _on(semi.device):
+            rc = _lib.lib().dfepe_sp_flatten_bwd(_ptr(semi), _ptr(g), B, 8 * Hc, 8 * Wc, _ptr(g_semi), _stream())
+        _lib.check(rc, "dfepe_sp_flatten_bwd")
+        return g_semi
+
+
+def sp_flatten(semi: Tensor) -> Tensor:
+    """semi [B,65,Hc,Wc] -> heatmap [B,1,8Hc,8Wc]: the softmax over the 65 channels without the dustbin, channel c of a cell at
+    pixel (c//8, c%8) of its 8x8 block; a NaN logit is read as 0 and receives no gradient (flattenDetection after set_nan2zero,
+    train_good_utils.py:741-743).  Differentiable w.r.t. semi."""
+    semi = _prep(semi, "semi")
+    _shape(semi, "semi", None, 65, None, None)
+    if semi.shape[2] < 1 or semi.shape[3] < 1:
+        raise ValueError(f"semi must have at least one cell, got {tuple(semi.shape)}")
+    _sp_pixels(8 * semi.shape[2], 8 * semi.shape[3], "sp_flatten")
+    return _SpFlattenFunction.apply(semi)
+
+
+def sp_nms_capacity(H: int, W: int, nms_dist: int) -> int:
+    """Rows of the point list of sp_nms: ceil(H/(d+1)) ceil(W/(d+1)), which no greedy NMS result exceeds."""
+    return int(_lib.lib().dfepe_sp_nms_capacity(int(H), int(W), int(nms_dist)))
+
+
+def sp_nms(heatmap: Tensor, conf_thresh: float, nms_dist: int, border_remove: Optional[int] = None) -> dict:
+    """heatmap [B,1,H,W] -> the greedy nms_fast of every image (heatmap_to_nms, train_good_utils.py:745): candidates h >=
+    conf_thresh visited by (confidence descending, row-major index ascending), kept iff no kept candidate lies within Chebyshev
+    distance nms_dist, border points (border_remove, default nms_dist) removed afterwards.  Returns dict(nms_map [B,1,H,W] of 0/1,
+    pts [B,cap,2] int32 (x, y) in row-major order, conf [B,cap], count [B] int32) with cap = sp_nms_capacity(H, W, nms_dist); rows
+    from count[b] on are 0.  Exact for any input; no host synchronisation; nothing differentiable."""
+    h = _prep(heatmap.detach(), "heatmap")
+    _shape(h, "heatmap", None, 1, None, None)
+    B, _, H, W = h.shape
+    d = int(nms_dist)
+    r = d if border_remove is None else int(border_remove)
+    if d < 0 or r < 0 or H < 1 or W < 1:
+        raise ValueError("sp_nms: nms_dist and border_remove must be >= 0 and the heatmap not empty")
+    _sp_pixels(H, W, "sp_nms")
+    L = _lib.lib()
+    dev = h.device
+    cap = int(L.dfepe_sp_nms_capacity(H, W, d))
+    out = {
+        "nms_map": torch.empty(B, 1, H, W, device=dev, dtype=torch.float32),
+        "pts": torch.empty(B, cap, 2, device=dev, dtype=torch.int32),
+        "conf": torch.empty(B, cap, device=dev, dtype=torch.float32),
+        "count": torch.empty(B, device=dev, dtype=torch.int32),
+    }
+    ws = _sp_bytes(L.dfepe_sp_nms_workspace_bytes(B, H, W), dev)
+    with _on(dev):
+        rc = L.dfepe_sp_nms(_ptr(h), B, H, W, float(conf_thresh), d, r, _ptr(ws), _ptr(out["nms_map"]), _ptr(out["pts"]), _ptr(out["conf"]),
+                            _ptr(out["count"]), _stream())
+    _lib.check(rc, "dfepe_sp_nms")
+    return out
+
+
+def _sp_list(pts: Tensor, count: Tensor, B: int, what: str):
+    if not torch.is_tensor(pts) or not pts.is_cuda or not torch.is_tensor(count) or not count.is_cuda:
+        raise _lib.DfepeError(f"{what}: pts and count must live on the GPU (this package has no CPU path)")
+    if pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] != 2 or pts.dtype != torch.int32 or count.shape != (B,) or count.dtype != torch.int32:
+        raise ValueError(f"{what}: pts must be int32 [B,cap,2] and count int32 [B], the outputs of sp_nms")
+    return pts.contiguous(), count.contiguous()
+
+
+class _SpSoftArgmaxFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, heat, pts, count, p, r, want_patches):
+        B, _, H, W = heat.shape
+        cap = pts.shape[1]
+        dev = heat.device
+        pred = torch.empty(B, cap, 2, device=dev, dtype=torch.float32)
+        patches = torch.empty(B, cap, p, p, device=dev, dtype=torch.float32) if want_patches else None
+        with _on(dev):
+            rc = _lib.lib().dfepe_sp_soft_argmax(_ptr(heat), _ptr(pts), _ptr(count), B, H, W, cap, p, r, _ptr(pred), _ptr(patches), _stream())
+        _lib.check(rc, "dfepe_sp_soft_argmax")
+        ctx.save_for_backward(heat, pts, count)
+        ctx.p, ctx.r = p, r
+        if patches is None:
+            return pred
+        ctx.mark_non_differentiable(patches)
+        return pred, patches
+
+    @staticmethod
+    def backward(ctx, g_pred, *_):
+        heat, pts, count = ctx.saved_tensors
+        B, _, H, W = heat.shape
+        cap = pts.shape[1]
+        dev = heat.device
+        g_pred = g_pred.contiguous().float()
+        L = _lib.lib()
+        ws = _sp_bytes(L.dfepe_sp_soft_argmax_bwd_workspace_bytes(B, H, W, cap), dev)
+        g_heat = torch.empty_like(heat)
+        with _on(dev):
+            rc = L.dfepe_sp_soft_argmax_bwd(_ptr(heat), _ptr(pts), _ptr(count), _ptr(g_pred), B, H, W, cap, ctx.p, ctx.r, _ptr(ws), _ptr(g_heat),
+                                            _stream())
+        _lib.check(rc, "dfepe_sp_soft_argmax_bwd")
+        return g_heat, None, None, None, None, None
+
+
+def sp_soft_argmax(heatmap: Tensor, pts: Tensor, count: Tensor, patch_size: int, border_remove: int, want_patches: bool = False):
+    """heatmap [B,1,H,W], pts [B,cap,2] int32 (x, y) and count [B] int32 from sp_nms -> pred [B,cap,2]: the sub-pixel offset (x, y) of
+    every listed point from the patch_size x patch_size patch around it (pred_soft_argmax, train_good_utils.py:747), 0 for rows
+    not listed and for a patch whose sum is not positive; with want_patches also the normalised patches [B,cap,p,p] (no gradient).
+    patch_size must be odd and <= 2 border_remove + 1, the border that sp_nms removed, so that every patch lies inside the image.
+    Differentiable w.r.t. the heatmap; the adjoint is a gather, bit-identical from run to run."""
+    h = _prep(heatmap, "heatmap")
+    _shape(h, "heatmap", None, 1, None, None)
+    B, _, H, W = h.shape
+    pts, count = _sp_list(pts, count, B, "sp_soft_argmax")
+    p, r = int(patch_size), int(border_remove)
+    if p < 1 or p % 2 == 0 or r < 0 or p > 2 * r + 1:
+        raise ValueError(f"sp_soft_argmax: patch_size must be odd and in [1, 2 border_remove + 1], got {p} with border_remove {r}")
+    if p > _lib.SP_MAX_PATCH:
+        raise _lib.DfepeError(f"sp_soft_argmax: patch_size {p}; at most {_lib.SP_MAX_PATCH}")
+    _sp_pixels(H, W, "sp_soft_argmax")
+    return _SpSoftArgmaxFunction.apply(h, pts, count, p, r, bool(want_patches))
+
+
+def sp_sample_desc(desc: Tensor, pts: Tensor, pred: Optional[Tensor], count: Tensor, align_corners: bool = True) -> Tensor:
+    """desc [B,D,Hc,Wc] coarse descriptors, positions pts + pred in pixels of the [8Hc,8Wc] image -> [B,cap,D]: the bilinear sample
+    (zero padding) at every listed position divided by its L2 norm, zeros for a zero norm and for rows not listed
+    (sample_desc_from_points).  align_corners=True is grid_sample's rule in the torch version that the reference pins.  Forward
+    only: the reference hands these descriptors to the matcher detached (train_good_utils.py:664, 686-688)."""
+    d = _prep(desc.detach(), "desc")
+    if d.dim() != 4 or min(d.shape[1:]) < 1:
+        raise ValueError(f"desc must be [B,D,Hc,Wc], got {tuple(d.shape)}")
+    B, D, Hc, Wc = d.shape
+    pts, count = _sp_list(pts, count, B, "sp_sample_desc")
+    cap = pts.shape[1]
+    pr = None
+    if pred is not None:
+        pr = _prep(pred.detach(), "pred")
+        _shape(pr, "pred", B, cap, 2)
+    _sp_pixels(8 * Hc, 8 * Wc, "sp_sample_desc")
+    out = torch.empty(B, cap, D, device=d.device, dtype=torch.float32)
+    with _on(d.device):
+        rc = _lib.lib().dfepe_sp_sample_desc(_ptr(d), _ptr(pts), _ptr(pr), _ptr(count), B, D, 8 * Hc, 8 * Wc, cap, int(bool(align_corners)),
+                                             _ptr(out), _stream())
+    _lib.check(rc, "dfepe_sp_sample_desc")
     return out
