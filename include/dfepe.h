@@ -1235,6 +1235,52 @@ int dfepe_sp_sample_desc(const float *desc, const int *pts, const float *pred, c
 int dfepe_gather_offsets_bwd(const float *g_offsets, int B, int N1, int N2, const int *m_idx1, const int *m_idx2, const int *choice,
                              int n_out, float *g_off1, float *g_off2, void *stream);
 
+/*
+ * The correspondence evaluation (run_eval_good.py --runCorr, :380-384 -> evaluation_epiDist.py val_feature), batched over B image
+ * pairs: the epipolar distance of every match under the ground-truth F (epi_dist_from_matches, deepFEPE/evaluation_epiDist.py:
+ * 276-326 -> val_rt -> epi_distance_np, deepFEPE/dsac_tools/utils_F.py:363-385) and Result_processor's table of inlier ratios by
+ * match score (deepFEPE/utils/eval_tools.py:27-174: inlier_ratio :70-104, get_mask :145-147, inlier_ratio_nested :151-162,
+ * inlier_ratio_from_est :164-174; ap_inlier_thd :113-137 sweeps the mask threshold; Exp_table_processor.get_result_dict :423-429
+ * calls inlier_ratio with mask_thd = 1.0).  No atomics of any kind; every output cell has one writer, so two calls on the same
+ * input are bit-identical; no host synchronisation, no allocation; all refusals are made before anything is launched, in the order
+ * in which they are listed.  dfepe_version() stays 154 with this addition: the number is pinned by existing tests, and nothing that
+ * existed changes.
+ *
+ * dfepe_inlier_table: one launch, one 256-thread workgroup per pair.
+ *   matches [B,N,4] fp32 (x1, y1, x2, y2; 16-byte aligned) with F [B,9] fp64 row-major, OR dist [B,N] fp32 (a distance computed
+ *     before): exactly one of matches and dist (with N == 0 neither is read and both may be NULL)
+ *   scores [B,N] fp32 or NULL (no mask: every match is kept; then Tm must be 1 and mask_thds is not read and may be NULL)
+ *   n_valid [B] int32 or NULL: pair b uses its first clamp(n_valid[b], 0, N) rows, as in dfepe_ransac_homography; NULL means all
+ *   inlier_thds [Ti], mask_thds [Tm] fp64 in device memory, 1 <= Ti, Tm <= 16
+ *   outputs, each may be NULL but not all of them:
+ *     cnt [B,Tm,Ti] int32   #{i: score_i < mask_thds[m] and dist_i < inlier_thds[t]}
+ *     num [B,Tm] int32      #{i: score_i < mask_thds[m]}                       (inlier_ratio's num_corrs)
+ *     ratio [B,Tm,Ti] fp64  (double)cnt / (double)num: 0 / 0 = NaN for a pair with nothing kept, as inlier_ratio_from_est gives
+ *     dist_out [B,N] fp32   the distance rounded once; rows past n_valid are 0
+ *   The distance is dist3 of epi_distance_np, in fp64 from the fp32 coordinates widened exactly, by the reference's sequence
+ *   (csrc/corr_eval_math.h spells out every association; no fused multiply-add):
+ *     a = y^T F;  nominator = |a . x|;  p = (F x)_12;  q = (F^T y)_12;  dist3 = nominator * (1 / sqrt(p.p) + 1 / sqrt(q.q))
+ *   with x = (x1, y1, 1), y = (x2, y2, 1).  The reciprocals come first, so F x = 0 gives 0 * inf = NaN where numpy gives it and a
+ *   non-zero numerator over a zero norm gives +inf.  Both comparisons are strict `<` in fp64 (the score widened to fp64, the
+ *   distance compared before it is rounded for dist_out; a dist input is widened to fp64).  A NaN passes neither test: a NaN
+ *   score is not kept; a kept match with a NaN distance is no inlier and stays in the denominator, as in numpy.
+ *   Refused: B or N < 0, Ti or Tm outside 1 .. 16, both matches and dist given, scores NULL with Tm != 1: INVALID_ARG.  Then
+ *   B == 0 returns OK and nothing is written.  With N > 0 neither matches nor dist; matches without F or not 16-byte aligned; a
+ *   null inlier_thds; scores with a null mask_thds; all four outputs NULL: INVALID_ARG.  N == 0 (or a pair with nothing valid)
+ *   is launched like any other: cnt and num 0, ratio NaN.
+ *
+ * dfepe_inlier_table_mean: one launch, one workgroup.
+ *   ratio [B,Tm,Ti] fp64 and num [B,Tm] int32 as written above -> mean [Tm,Ti] fp64 = the sum over the pairs in index order
+ *   (b = 0, 1, ...: the order of numpy's table.mean(axis=0)), divided by B; a NaN ratio makes the mean NaN, B == 0 gives 0 / 0 =
+ *   NaN.  num_T [Tm,B] int32 = num transposed, the layout ap_inlier_thd returns.  Either output may be NULL, not both.
+ *   Refused: B < 0, Ti or Tm outside 1 .. 16, both outputs NULL, with B > 0 a null ratio with mean or a null num with num_T:
+ *   INVALID_ARG.  B == 0 is launched (mean is NaN).
+ */
+int dfepe_inlier_table(const float *matches, const double *F, const float *dist, const float *scores, const int *n_valid, int B, int N,
+                       const double *inlier_thds, int Ti, const double *mask_thds, int Tm, int *cnt, int *num, double *ratio,
+                       float *dist_out, void *stream);
+int dfepe_inlier_table_mean(const double *ratio, const int *num, int B, int Tm, int Ti, double *mean, int *num_T, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

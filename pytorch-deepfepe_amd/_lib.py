@@ -44,6 +44,7 @@ DETECTOR_EVAL_MAX_N = 4096  # dfepe_keypoint_repeatability (points per image), d
 SP_MAX_PIXELS = 1 << 24  # dfepe_sp_*: pixels per image (sp::kMaxPixels, csrc/sp_process_math.h)
 SP_LDS_PIXELS = 12288  # dfepe_sp_nms: pixels per image up to which no workspace is needed (sp::kLdsPixels)
 SP_MAX_PATCH = 63  # dfepe_sp_soft_argmax: largest patch_size (sp::kMaxPatch)
+INLIER_TABLE_MAX_THDS = 16  # dfepe_inlier_table: inlier thresholds per call, and mask thresholds per call (ce::kMaxThds)
 
 _P = c_void_p
 _SIGNATURES = {
@@ -157,6 +158,8 @@ _SIGNATURES = {
     "dfepe_sp_soft_argmax_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "dfepe_sp_sample_desc": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "dfepe_gather_offsets_bwd": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
+    "dfepe_inlier_table": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
+    "dfepe_inlier_table_mean": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

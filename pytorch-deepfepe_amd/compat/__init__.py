@@ -18,20 +18,24 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.evaluate_frontend          ->   compat.evaluate_frontend (matching score, nn mean AP, the five numbers per pair)
     deepFEPE.dsac_tools.utils_vis       ->   compat.utils_vis       (reproj_and_scatter without the drawing)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC hypothesis loop, all hypotheses per launch)
-    superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker.nn_match_two_way only)
+    superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker: nn_match_two_way and the two-frame state)
     superpoint.models.model_utils,      ->   compat.superpoint_process (flattenDetection, SuperPointNet_process: what
     superpoint.utils.utils                                          process_SP_output calls; the network stays the caller's)
     deepFEPE.utils.eval_tools           ->   compat.eval_tools      (Exp_table_processor's odometry methods: get_abs_poses,
                                                                     compensate_poses, compute_pose_error, pose_seq_ate; plus
-                                                                    relative_pose_cam_to_body and the on-device odometry_summary)
+                                                                    relative_pose_cam_to_body and the on-device odometry_summary;
+                                                                    Result_processor, the correspondence table)
+    deepFEPE.evaluation_epiDist         ->   compat.evaluation_epiDist (epi_dist_from_matches, process_grey2tensor; the on-device
+                                                                    correspondence_eval_batch)
 
     (no counterpart: the reference's agent is eager)  compat.CapturedStep  (its training step as one replayed hipGraph)
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
+from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, evaluation_epiDist, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401
 from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
 from .detector_evaluation import compute_repeatability, compute_repeatability_batch  # noqa: F401
 from .evaluate_frontend import frontend_metrics_batch  # noqa: F401
+from .evaluation_epiDist import correspondence_eval_batch  # noqa: F401
 from .utils_opencv import findHomography, findHomography_batch  # noqa: F401

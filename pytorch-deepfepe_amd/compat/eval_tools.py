@@ -2,7 +2,8 @@
 get_abs_poses :268-284, compute_pose_error :309-331, pose_seq_ate :334-375) and of the camera-to-body step in front of it
 (relative_pose_cam_to_body, the function nested at Train_model_pipeline.py:1098-1108), backed by dfepe_pose_chain and
 dfepe_snippet_errors (include/dfepe.h); and the step the reference leaves to an external tool, the KITTI odometry table
-(kitti_odometry_eval, odometry_table, read_kitti_poses, write_kitti_result at the end of this file).
+(kitti_odometry_eval, odometry_table, read_kitti_poses, write_kitti_result); and of the correspondence table, Result_processor (eval_tools.py:27-174, at the end of this file), backed by
+dfepe_inlier_table and dfepe_inlier_table_mean.
 
 Two surfaces:
 
@@ -19,6 +20,7 @@ as float64 scalars that carry float32 precision (the kernel's error array is flo
 """
 from __future__ import annotations
 
+import logging
 import os
 
 import numpy as np
@@ -263,3 +265,144 @@ def write_kitti_result(out_dir, seq, result) -> None:
         for label, key in zip(KITTI_RESULT_LINES, ("t_rel", "r_rel", "ATE", "RPE_trans", "RPE_rot")):
             f.write(f"{label}: \t {val(key):.3f} \n")
         f.write("\n")
+
+
+# ---- the correspondence table (run_eval_good.py --runCorr -> evaluation_epiDist.py val_feature -> Result_processor) ---------------
+def _ship(dev, *arrays):
+    """Host arrays -> device tensors of the same dtypes and shapes through ONE host-to-device copy: the arrays are laid one after
+    the other (each on a 16-byte boundary) in a byte buffer, and the device buffer is cut up again."""
+    arrays = [np.ascontiguousarray(a) for a in arrays]
+    offs, total = [], 0
+    for a in arrays:
+        offs.append(total)
+        total += (a.nbytes + 15) // 16 * 16
+    blob = np.zeros(max(total, 16), np.uint8)
+    for a, o in zip(arrays, offs):
+        blob[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    t = torch.from_numpy(blob).to(dev)
+    return [t[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).view(a.shape) for a, o in zip(arrays, offs)]
+
+
+def _chunks(values, size=_lib.INLIER_TABLE_MAX_THDS):
+    return [values[i:i + size] for i in range(0, len(values), size)]
+
+
+def _corr_tables(result_list, thd_list, mask_list, mask_thds):
+    """Per-pair host arrays -> (mean [Tm,Ti], num_T [Tm,B], ratio [B,Tm,Ti]) numpy: padded once to [B,Nmax] plus n_valid, shipped
+    in one copy, evaluated by ops.inlier_table and ops.inlier_table_mean (one pair of launches per 16 x 16 thresholds)."""
+    ests = [np.asarray(re, np.float32).reshape(-1) for re in result_list]
+    masks = None
+    if mask_list is not None:
+        masks = []
+        for i, est_arr in enumerate(ests):
+            m = np.asarray(mask_list[i], np.float32).reshape(-1)
+            assert (
+                m.shape[0] == est_arr.shape[0]
+            ), "mask size not equal to estimated arr"
+            masks.append(m)
+    ithds = [float(t) for t in thd_list]
+    mthds = [float(t) for t in mask_thds] if masks is not None else [0.0]
+    B, Ti, Tm = len(ests), len(ithds), len(mthds)
+    if B == 0 or Ti == 0 or Tm == 0:
+        return np.full((Tm, Ti), np.nan), np.zeros((Tm, B), np.int64), np.zeros((B, Tm, Ti))
+    N = max(len(e) for e in ests)
+    dist, sc = np.zeros((B, N), np.float32), np.zeros((B, N), np.float32)
+    for b, e in enumerate(ests):
+        dist[b, :len(e)] = e
+        if masks is not None:
+            sc[b, :len(e)] = masks[b]
+    nv = np.asarray([len(e) for e in ests], np.int32)
+    d_dist, d_sc, d_nv, d_it, d_mt = _ship(_dev(), dist, sc, nv, np.asarray(ithds, np.float64), np.asarray(mthds, np.float64))
+    mean, num_T, ratio = np.zeros((Tm, Ti)), np.zeros((Tm, B), np.int64), np.zeros((B, Tm, Ti))
+    for m0 in range(0, Tm, _lib.INLIER_TABLE_MAX_THDS):
+        m1 = min(m0 + _lib.INLIER_TABLE_MAX_THDS, Tm)
+        for t0 in range(0, Ti, _lib.INLIER_TABLE_MAX_THDS):
+            t1 = min(t0 + _lib.INLIER_TABLE_MAX_THDS, Ti)
+            r = ops.inlier_table(dist=d_dist, scores=d_sc if masks is not None else None, n_valid=d_nv, inlier_thds=d_it[t0:t1],
+                                 mask_thds=d_mt[m0:m1] if masks is not None else None, want=("num", "ratio"))
+            mn, nT = ops.inlier_table_mean(r["ratio"], r["num"])
+            mean[m0:m1, t0:t1], num_T[m0:m1], ratio[:, m0:m1, t0:t1] = mn.cpu().numpy(), nT.cpu().numpy(), r["ratio"].cpu().numpy()
+    return mean, num_T, ratio
+
+
+class Result_processor(object):
+    """The reference's Result_processor (deepFEPE/utils/eval_tools.py:27-174) with its constructor, signatures and return types;
+    the tables are computed on the device (dfepe_inlier_table, dfepe_inlier_table_mean).  Distances and scores travel as float32,
+    which is what ops.inlier_table's dist_out and the matcher's scores are; a float64 list is rounded to float32 first."""
+
+    def __init__(self, result_dict_entry):
+        self.result_dict_all = {}
+        self.result_dict_entry = result_dict_entry
+        self.result_processed = {}
+        for ent in result_dict_entry:
+            self.result_dict_all[ent] = []
+
+    def add_config(self, config):
+        pass
+
+    def load_result(self, result_dict):
+        """result_dict: dictionary with entries"""
+        for ent in self.result_dict_entry:
+            if ent not in result_dict:
+                logging.warning(f"{ent} not in the result dictionary")
+            else:
+                self.result_dict_all[ent].append(result_dict[ent])
+
+    def output_result(self, method=[None], **params):
+        for m in method:
+            if m is not None:
+                func = getattr(self, m)
+                func(params[m])
+
+    def inlier_ratio(self, result_list, thd_list, mask_list=None, mask_thd=1, if_print=False):
+        """result_list: one nested result of a sequence (per pair, the distances of its matches); mask_list: the scores of the
+        results (mscores for correspondences) -> {"inlier_ratio": np[len(thd_list)] = the per-pair ratios' mean, "num_corrs":
+        np[pairs]}.  A pair with nothing kept has the ratio 0 / 0 = NaN, and so has the mean, as in the reference.  val_feature
+        ends by passing an entry NAME as result_list (evaluation_epiDist.py:243-245), which the reference's loop cannot digest; a
+        string is looked up in result_dict_all here."""
+        if isinstance(result_list, str):
+            result_list = self.result_dict_all[result_list]
+        mean, num_T, _ = _corr_tables(result_list, thd_list, mask_list, [mask_thd])
+        results = {"inlier_ratio": mean[0], "num_corrs": num_T[0]}
+        if if_print:
+            print(f"inlier ratio thd: {thd_list}, result: {results}")
+        return results
+
+    def get_entry_from_result(self, entry, if_print=False):
+        if entry in self.result_dict_all:
+            return self.result_dict_all[entry]
+        else:
+            logging.error(f"{entry} is not in the dictionary.")
+
+    def ap_inlier_thd(self, inlier_entry, inlier_thds, mask_thds, mask_entry="mscores", if_print=False):
+        """Unpinned: the reference's method passes a ``mask_entry=`` keyword that its inlier_ratio does not take, so it raises
+        there.  This is its evident intent: both entries are looked up in result_dict_all, and the inlier ratios under every mask
+        threshold are computed in ONE launch -> {"inlier_thd": np[len(mask_thds), len(inlier_thds)], "num_corrs":
+        np[len(mask_thds), pairs]}."""
+        result_list = self.result_dict_all[inlier_entry]
+        mask_list = None if mask_entry is None else self.result_dict_all[mask_entry]
+        table, num_corrs, _ = _corr_tables(result_list, inlier_thds, mask_list, list(mask_thds))
+        if mask_list is None:
+            table, num_corrs = np.repeat(table, len(mask_thds), 0), np.repeat(num_corrs, len(mask_thds), 0)
+        print(f"table: {table.shape}")
+        results = {"inlier_thd": table, "num_corrs": num_corrs}
+        if if_print:
+            print(f"inlier ratio thd: {inlier_thds}, mask thd: {list(mask_thds)}, result: {results}")
+        return results
+
+    def save_result(self, filename, item):
+        if item == "result_dict_all":
+            np.savez_compressed(filename, **self.result_dict_all)
+
+    @staticmethod
+    def get_mask(arr, thd):
+        return np.array(arr) < thd
+
+    def inlier_ratio_nested(self, est_nested, thd_list):
+        """est_nested: per pair, the distances of its matches -> np[len(thd_list)], the mean over the pairs of the inlier ratios"""
+        return _corr_tables(est_nested, thd_list, None, None)[0][0]
+
+    @staticmethod
+    def inlier_ratio_from_est(est_arr, thd_list):
+        """inlier_ratio_from_est(est_arr, thd_list) -> list"""
+        return list(_corr_tables([est_arr], thd_list, None, None)[2][0, 0])

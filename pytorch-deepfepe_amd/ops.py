@@ -2008,3 +2008,100 @@ def sp_sample_desc(desc: Tensor, pts: Tensor, pred: Optional[Tensor], count: Ten
                                              _ptr(out), _stream())
     _lib.check(rc, "dfepe_sp_sample_desc")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# correspondence evaluation (evaluation_epiDist.py val_feature, eval_tools.Result_processor): inlier ratios by match score
+# ------------------------------------------------------------------------------------------------
+INLIER_TABLE_OUTPUTS = ("cnt", "num", "ratio", "dist_out")
+
+
+def _thds_arg(thds, dev, name: str) -> Tensor:
+    """A threshold list as a float64 [T] device tensor: a device tensor is taken as it is; host values are uploaded (inside a
+    graph capture pass a device tensor)."""
+    if torch.is_tensor(thds):
+        if not thds.is_cuda:
+            raise _lib.DfepeError(f"{name} must live on the GPU when it is a tensor (this package has no CPU path)")
+        t = thds.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        t = torch.tensor([float(v) for v in thds], dtype=torch.float64).to(dev)
+    if t.dim() != 1 or not 1 <= t.shape[0] <= _lib.INLIER_TABLE_MAX_THDS:
+        raise ValueError(f"{name} must hold 1 .. {_lib.INLIER_TABLE_MAX_THDS} thresholds, got shape {tuple(t.shape)}")
+    return t
+
+
+def inlier_table(matches: Optional[Tensor] = None, F: Optional[Tensor] = None, scores: Optional[Tensor] = None,
+                 n_valid: Optional[Tensor] = None, inlier_thds=(1.0,), mask_thds=None, want=("cnt", "num", "ratio"),
+                 dist: Optional[Tensor] = None) -> dict:
+    """matches [B,N,4] pixels (x1, y1, x2, y2) with F [B,3,3], or dist [B,N] (a distance computed before), exactly one of the two;
+    scores [B,N] or None (no mask: every match is kept, and mask_thds must be None or hold one value); n_valid [B] int32 on the
+    device or None: pair b uses its first clamp(n_valid[b], 0, N) rows; inlier_thds [Ti], mask_thds [Tm] (1 .. 16 each; device
+    tensors, or host values that are uploaded) -> dict of the outputs named in ``want``:
+      cnt [B,Tm,Ti] int32 = #{score < mask_thd and dist < inlier_thd}, num [B,Tm] int32 = #{score < mask_thd} (num_corrs),
+      ratio [B,Tm,Ti] float64 = cnt / num (NaN for a pair with nothing kept), dist_out [B,N] float32 (0 past n_valid)
+    Result_processor.inlier_ratio (deepFEPE/utils/eval_tools.py:70-104) over epi_distance_np's dist3 (dsac_tools/utils_F.py:363-385)
+    for B pairs, Tm mask thresholds and Ti inlier thresholds in one launch; the distance and both strict comparisons are fp64.
+    No host synchronisation; capturable."""
+    if (matches is None) == (dist is None):
+        raise ValueError("inlier_table takes matches (with F) or dist, exactly one of the two")
+    want = tuple(want)
+    if not want or any(w not in INLIER_TABLE_OUTPUTS for w in want):
+        raise ValueError(f"want must name at least one of {INLIER_TABLE_OUTPUTS}, got {want}")
+    if matches is not None:
+        m = _prep(matches, "matches")
+        _shape(m, "matches (pixel x1,y1,x2,y2)", None, None, 4)
+        B, N = m.shape[0], m.shape[1]
+        if F is None:
+            raise ValueError("inlier_table: matches need F")
+        Fd, d, dev = _h9(F, "F", B), None, m.device
+    else:
+        d = _prep(dist, "dist")
+        _shape(d, "dist", None, None)
+        B, N = d.shape
+        m, Fd, dev = None, None, d.device
+    sc = None
+    if scores is not None:
+        sc = _prep(scores, "scores")
+        _shape(sc, "scores", B, N)
+    elif mask_thds is not None and len(mask_thds) != 1:
+        raise ValueError("inlier_table: without scores nothing is masked; mask_thds must be None or hold one value")
+    nv = _n_valid_arg(n_valid, B, dev, "inlier_table")
+    it = _thds_arg(inlier_thds, dev, "inlier_thds")
+    mt = _thds_arg(mask_thds, dev, "mask_thds") if sc is not None and mask_thds is not None else None
+    if sc is not None and mt is None:
+        raise ValueError("inlier_table: scores need mask_thds")
+    Ti, Tm = it.shape[0], (mt.shape[0] if mt is not None else 1)
+    out = {
+        "cnt": torch.empty(B, Tm, Ti, device=dev, dtype=torch.int32) if "cnt" in want else None,
+        "num": torch.empty(B, Tm, device=dev, dtype=torch.int32) if "num" in want else None,
+        "ratio": torch.empty(B, Tm, Ti, device=dev, dtype=torch.float64) if "ratio" in want else None,
+        "dist_out": torch.empty(B, N, device=dev, dtype=torch.float32) if "dist_out" in want else None,
+    }
+    with _on(dev):
+        rc = _lib.lib().dfepe_inlier_table(_ptr(m), _ptr(Fd), _ptr(d), _ptr(sc), _ptr(nv), B, N, _ptr(it), Ti, _ptr(mt), Tm, _ptr(out["cnt"]),
+                                           _ptr(out["num"]), _ptr(out["ratio"]), _ptr(out["dist_out"]), _stream())
+    _lib.check(rc, "dfepe_inlier_table")
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def inlier_table_mean(ratio: Tensor, num: Tensor):
+    """ratio [B,Tm,Ti] float64, num [B,Tm] int32 (inlier_table's) -> (mean [Tm,Ti] float64, num_T [Tm,B] int32): the table's mean
+    over the pairs, added in index order and NaN-propagating as numpy's table.mean(axis=0) is (eval_tools.py:99-100), and the
+    counts in the layout ap_inlier_thd returns.  B == 0 gives a NaN mean.  One launch, no host synchronisation; capturable."""
+    for t, name in ((ratio, "ratio"), (num, "num")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.DfepeError(f"{name} must live on the GPU (this package has no CPU path)")
+    _shape(ratio, "ratio", None, None, None)
+    B, Tm, Ti = ratio.shape
+    _shape(num, "num", B, Tm)
+    if not (1 <= Tm <= _lib.INLIER_TABLE_MAX_THDS and 1 <= Ti <= _lib.INLIER_TABLE_MAX_THDS):
+        raise ValueError(f"ratio must be [B,Tm,Ti] with 1 .. {_lib.INLIER_TABLE_MAX_THDS} thresholds each, got {tuple(ratio.shape)}")
+    r = ratio.to(torch.float64).contiguous()
+    n = num.to(torch.int32).contiguous()
+    dev = r.device
+    mean = torch.empty(Tm, Ti, device=dev, dtype=torch.float64)
+    num_T = torch.empty(Tm, B, device=dev, dtype=torch.int32)
+    with _on(dev):
+        rc = _lib.lib().dfepe_inlier_table_mean(_ptr(r), _ptr(n), B, Tm, Ti, _ptr(mean), _ptr(num_T), _stream())
+    _lib.check(rc, "dfepe_inlier_table_mean")
+    return mean, num_T
