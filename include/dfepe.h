@@ -1281,6 +1281,62 @@ int dfepe_inlier_table(const float *matches, const double *F, const float *dist,
                        float *dist_out, void *stream);
 int dfepe_inlier_table_mean(const double *ratio, const int *num, int B, int Tm, int Ti, double *mean, int *num_T, void *stream);
 
+/*
+ * Adjoints of the epipolar distances (csrc/epi_adjoint.hip, csrc/epi_adjoint_math.h): the gradients of dfepe_epi_metrics with
+ * respect to F, X and Y, the gradient of the epipolar residual with respect to its points, and the reduced loss sum_n w e with its
+ * adjoint.  The reference's _sym_epi_dist, _sampson_dist, _epi_distance and compute_epi_residual (deepFEPE/dsac_tools/utils_F.py:
+ * 291-361, 400-413) are plain torch and so differentiable in every argument; get_loss_softmax (train_good_utils.py:55-61), HLoss
+ * (dsac_tools/H_loss.py) and the soft inlier count of dsac_tools/dsac.py rely on that.  fp32 in and out, fp64 inside, every output
+ * rounded once.  No atomics, no allocation, no host synchronisation: the calls can be captured in a hipGraph, and a pair's result is
+ * the same bits on every run and whatever else is in the batch.  dfepe_version() stays 154 with this addition: the number is pinned
+ * by existing tests, and nothing that existed changes.
+ *
+ * `kind`, DFEPE_EPI_HOMOGENEOUS, `clamp_at` (< 0: no clamp; kind 0 only) and `eps` mean what they mean for dfepe_epi_metrics.  With
+ * x = (x0, x1, x2) and y likewise (third coordinate the constant 1, without a gradient, unless DFEPE_EPI_HOMOGENEOUS), a = F x,
+ * b = F^T y, s = y^T F x, A = a0^2 + a1^2, Q = b0^2 + b1^2:
+ *   kind 0   e = s^2 (1/(A+eps) + 1/(Q+eps)) =: s^2 R    de = 2 s R ds - s^2 (dA/(A+eps)^2 + dQ/(Q+eps)^2), where e <= clamp_at
+ *            (torch.clamp(max=) passes the gradient AT the bound), 0 elsewhere
+ *   kind 1   e = s^2 / (A+Q)                             de = 2 s ds/(A+Q) - s^2 (dA+dQ)/(A+Q)^2
+ *   kind 2   d1 = |s|/sqrt(A), d2 = |s|/sqrt(Q), planes ((d1+d2)/2, d1, d2); the three upstream planes g_out [3,B,N] are combined
+ *            per point; dd1 = sign(s) ds/sqrt(A) - |s| dA/(2 A^(3/2)), dd2 likewise; sign(0) = 0
+ *   ds/dF_rc = y_r x_c, ds/dx = b, ds/dy = a;  dA/dF_rc = 2 a_r x_c [r<2], dA/dx_c = 2 (a0 F_0c + a1 F_1c);
+ *   dQ/dF_rc = 2 b_c y_r [c<2], dQ/dy_r = 2 (b0 F_r0 + b1 F_r1).
+ * A point whose forward value is not finite (F x = 0 with eps = 0, a NaN input) may produce anything in its own g_X, g_Y (g_w) rows
+ * and in its own pair's g_F (sum); it changes no bit of any other pair's outputs or of any other point's rows.
+ *
+ * Launch shape: a workgroup of 256 lanes owns a chunk of P = dfepe_epi_adjoint_chunk() consecutive points of one pair.  The nine
+ * fp64 partial sums of g_F (the one of the loss) are reduced in a fixed order: per lane, across the wavefront, the four wavefront
+ * totals in order.  With N <= P the workgroup writes the result and there is one launch; otherwise its doubles go to `workspace`
+ * [B, ceil(N/P), 9] (dfepe_epi_adjoint_workspace_bytes(B, N) bytes, 8-byte aligned, contents irrelevant) and a second launch on the
+ * same stream adds the chunks in ascending order.  The workspace is only touched for g_F and for the loss sum.
+ *
+ * Refusals, made on the host before any HIP call, in this order: B or N < 0, a kind outside 0..2 (| DFEPE_EPI_HOMOGENEOUS), or
+ * clamp_at >= 0 on kinds 1 and 2: INVALID_ARG.  Then B == 0 or N == 0 returns OK: nothing is launched and nothing written.  A NULL
+ * input, every output NULL, [B,N,2] points or point gradients that are not 8-byte aligned, a NULL or misaligned workspace when it
+ * is needed (N > P and g_F or the sum asked for): INVALID_ARG.  B * N > 2^31 - 1: UNSUPPORTED (the grid has B * ceil(N/P) blocks).
+ *
+ * dfepe_epi_metrics_bwd: g_out [B,N] (kinds 0, 1) or [3,B,N] (kind 2) -> g_F [B,9], g_X, g_Y [B,N,2|3]; an output that is NULL is
+ *   skipped (for g_F the sums and the second launch too); whichever are asked for, each has the same bits.
+ * dfepe_epi_residual_bwd_pts: compute_epi_residual w.r.t. its points (w.r.t. F: dfepe_epi_residual_bwd).  pts1, pts2 [B,N,3], F
+ *   [B,9], g_out [B,N] -> g_pts1, g_pts2 [B,N,3] (either may be NULL).  With l1 = F^T x2, l2 = F x1, dd = x2^T F x1, n = |l[:2]|,
+ *   i = 1/(n + 1e-6), S = i1 + i2, d = |dd| S:  dd/dx1 = sign(dd) S l1 - k2 F[:2,:]^T l2[:2],  dd/dx2 = sign(dd) S l2 -
+ *   k1 F[:,:2] l1[:2],  k = |dd| i^2 / n (0 where n = 0); the gradient passes where d <= clamp_at; sign(0) = 0.
+ * dfepe_epi_loss_fwd: sum_out [B] = sum_n w[b,n] e[b,n] (w [B,N] or NULL = 1); e is kind 0 or 1, or the first plane of kind 2.
+ *   The per-point values are never written.
+ * dfepe_epi_loss_bwd: g_sum [B] -> g_F, g_X, g_Y as above with the upstream g_sum[b] w[b,n], and g_w [B,N] = g_sum[b] e[b,n]
+ *   (recomputed); each may be NULL, not all.
+ */
+int dfepe_epi_adjoint_chunk(void);
+size_t dfepe_epi_adjoint_workspace_bytes(int B, int N);
+int dfepe_epi_metrics_bwd(void *stream, int kind, const float *F, const float *X, const float *Y, int B, int N, float clamp_at,
+                          float eps, const float *g_out, float *g_F, float *g_X, float *g_Y, void *workspace);
+int dfepe_epi_residual_bwd_pts(void *stream, const float *pts1, const float *pts2, const float *F, int B, int N, float clamp_at,
+                               const float *g_out, float *g_pts1, float *g_pts2);
+int dfepe_epi_loss_fwd(void *stream, int kind, const float *F, const float *X, const float *Y, const float *w, int B, int N,
+                       float clamp_at, float eps, float *sum_out, void *workspace);
+int dfepe_epi_loss_bwd(void *stream, int kind, const float *F, const float *X, const float *Y, const float *w, int B, int N,
+                       float clamp_at, float eps, const float *g_sum, float *g_F, float *g_X, float *g_Y, float *g_w, void *workspace);
+
 #ifdef __cplusplus
 }
 #endif

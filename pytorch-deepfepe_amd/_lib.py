@@ -160,6 +160,12 @@ _SIGNATURES = {
     "dfepe_gather_offsets_bwd": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
     "dfepe_inlier_table": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
     "dfepe_inlier_table_mean": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "dfepe_epi_adjoint_chunk": (c_int, []),
+    "dfepe_epi_adjoint_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dfepe_epi_metrics_bwd": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
+    "dfepe_epi_residual_bwd_pts": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
+    "dfepe_epi_loss_fwd": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P]),
+    "dfepe_epi_loss_bwd": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

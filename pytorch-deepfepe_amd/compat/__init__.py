@@ -6,7 +6,9 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.models.ErrorEstimators     ->   compat.ErrorEstimators (stock PyTorch; not part of the hot path)
     deepFEPE.dsac_tools.utils_F         ->   compat.utils_F
     deepFEPE.dsac_tools.utils_geo       ->   compat.utils_geo
-    deepFEPE.train_good_utils           ->   compat.train_good_utils (get_all_loss_DeepF, get_Rt_loss, get_matches_from_SP)
+    deepFEPE.train_good_utils           ->   compat.train_good_utils (get_all_loss_DeepF, get_Rt_loss, get_matches_from_SP,
+                                                                    get_loss_softmax: differentiable through the kernel's adjoint)
+    deepFEPE.dsac_tools.H_loss          ->   compat.H_loss          (HLoss: the mean Sampson distance, differentiable likewise)
     deepFEPE.dsac_tools.utils_misc      ->   compat.utils_misc      (homogeneous / rigid-transform helpers, crop_or_pad_choice,
                                                                     get_virt_x1x2*: the F-loss's virtual points, no cv2)
     deepFEPE.dsac_tools.utils_opencv    ->   compat.utils_opencv    (recover_camera_opencv: the 8-point RANSAC baseline, no cv2;
@@ -32,7 +34,7 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, evaluation_epiDist, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
+from . import DeepFNet, ErrorEstimators, H_loss, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, evaluation_epiDist, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401
 from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
 from .detector_evaluation import compute_repeatability, compute_repeatability_batch  # noqa: F401

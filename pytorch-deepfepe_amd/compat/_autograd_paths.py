@@ -3,11 +3,13 @@
 The reference's _sym_epi_dist, _sampson_dist, _epi_distance, compute_epi_residual, _get_M2s, _R_to_q, _F_from_XY and _E_from_XY
 are plain torch code and therefore differentiable in every argument (deepFEPE/dsac_tools/utils_F.py:104-155,223-275,291-361,
 400-413,478-498; utils_geo.py:58-86); its legacy callers use that (train_good_utils.py:55-61, dsac_tools/dsac.py:138-176).  The
-mirrors in compat.utils_F / compat.utils_geo are raw kernel launches with no adjoint (the hot path has its own fused adjoints:
-ops.w8pt, ops.floss, ops.pose_errors).  When -- and only when -- one of their inputs requires grad, the mirrors evaluate the same
-formulas here instead, as torch expressions on the tensors' own (GPU) device, so that autograd gives the caller the reference's
-gradients; without a gradient request nothing in this file runs.  Each function restates the published formula, batched over
-leading dimensions; the GPU tests hold the values to the kernels' and the gradients to float64 autograd of the oracle."""
+mirrors of _get_M2s, _R_to_q, _F_from_XY and _E_from_XY in compat.utils_F / compat.utils_geo are raw kernel launches with no adjoint
+(the hot path has its own fused adjoints: ops.w8pt, ops.floss, ops.pose_errors).  When -- and only when -- one of their inputs
+requires grad, those mirrors evaluate the same formulas here instead, as torch expressions on the tensors' own (GPU) device, so that
+autograd gives the caller the reference's gradients; without a gradient request nothing in this file runs.  The four epipolar
+distances have HIP adjoints since csrc/epi_adjoint.hip and no longer come here; their expressions below stay as a second comparator
+of the tests and as the earlier route that scripts/epi_adjoint_time.py times.  Each function restates the published formula, batched
+over leading dimensions; the GPU tests hold the values to the kernels' and the gradients to float64 autograd of the oracle."""
 import torch
 
 

@@ -14,6 +14,16 @@ def mean_list(lst):
     return sum(lst) / len(lst)
 
 
+def get_loss_softmax(F_gts, pts1_virt, pts2_virt, clamp_at):
+    """(losses.mean(), losses) of the clamped squared symmetric epipolar distance of homogeneous virtual points [B,M,3] under
+    F_gts [B,3,3] (train_good_utils.py:55-61).  Differentiable in all three through the kernel's adjoint (ops.epi_metrics).  A
+    caller that needs the mean alone can take ops.epi_loss(0, ..., eps=1e-10, reduction="mean"), which never writes the losses."""
+    from . import utils_F
+
+    losses = utils_F._sym_epi_dist(F_gts, pts1_virt, pts2_virt, if_homo=True, clamp_at=clamp_at)
+    return losses.mean(), losses
+
+
 def get_unique(xs, topk, matches_good_unique_nums):
     """top-k of the first `unique_num` entries per sample (train_good_utils.py get_unique)."""
     out = []

@@ -54,11 +54,9 @@ def _normalize_XY_batch(X, Y):
 
 
 def compute_epi_residual(pts1, pts2, F, clamp_at=0.5):
-    """Symmetric epipolar residual, [B,N] (utils_F.py:400-413).  The kernel (with its adjoint w.r.t. F: what the F-loss needs; the
-    recurrent model's in-loop residual with point gradients comes out of the fit itself, ops.w8pt); when the POINTS require grad,
-    the same formula through torch autograd (_autograd_paths)."""
-    if _ap.wants_grad(pts1, pts2):
-        return _ap.epi_residual(_gpu(pts1), _gpu(pts2), _gpu(F), clamp_at)
+    """Symmetric epipolar residual, [B,N] (utils_F.py:400-413).  The kernel, with its adjoints: w.r.t. F (what the F-loss needs)
+    and w.r.t. the points (dfepe_epi_residual_bwd_pts; the recurrent model's in-loop residual with point gradients comes out of
+    the fit itself, ops.w8pt).  The values are the kernel's whether or not a gradient is asked for."""
     return ops.epi_residual(_gpu(pts1), _gpu(pts2), _gpu(F), clamp_at)
 
 
@@ -149,26 +147,23 @@ def _epi_args(what, F, X, Y, if_homo):
 
 
 def _sym_epi_dist(F, X, Y, if_homo=False, clamp_at=None):
-    """Squared symmetric epipolar distance (utils_F.py:310-339); the 1e-10 guard only in the batched form (:329)."""
-    if _ap.wants_grad(F, X, Y):  # the reference's gradients (legacy callers: train_good_utils.py:55-61), see _autograd_paths
-        return _ap.sym_epi_dist(_gpu(F), _gpu(X), _gpu(Y), if_homo, clamp_at, eps=0.0 if torch.as_tensor(X).dim() == 2 else 1e-10)
+    """Squared symmetric epipolar distance (utils_F.py:310-339); the 1e-10 guard only in the batched form (:329).  Differentiable in
+    F, X and Y through the kernel's own adjoint (ops.epi_metrics; legacy callers: train_good_utils.py:55-61)."""
     F, X, Y, single = _epi_args("_sym_epi_dist", F, X, Y, if_homo)
     out = ops.epi_metrics(0, F, X, Y, clamp_at=clamp_at, eps=0.0 if single else 1e-10)
     return out[0] if single else out
 
 
 def _sampson_dist(F, X, Y, if_homo=False):
-    if _ap.wants_grad(F, X, Y):  # dsac_tools/dsac.py:138-176 differentiates the soft inlier count through this
-        return _ap.sampson_dist(_gpu(F), _gpu(X), _gpu(Y), if_homo)
+    """Sampson distance (utils_F.py:291-308); differentiable like _sym_epi_dist (dsac_tools/dsac.py:56-76 differentiates the soft
+    inlier count through it, H_loss.py its mean)."""
     F, X, Y, single = _epi_args("_sampson_dist", F, X, Y, if_homo)
     out = ops.epi_metrics(1, F, X, Y)
     return out[0] if single else out
 
 
 def _epi_distance(F, X, Y, if_homo=False):
-    """Returns ((d1+d2)/2, d1, d2) (utils_F.py:341-361)."""
-    if _ap.wants_grad(F, X, Y):
-        return _ap.epi_distance(_gpu(F), _gpu(X), _gpu(Y), if_homo)
+    """Returns ((d1+d2)/2, d1, d2) (utils_F.py:341-361); differentiable like _sym_epi_dist."""
     F, X, Y, single = _epi_args("_epi_distance", F, X, Y, if_homo)
     out = ops.epi_metrics(2, F, X, Y)
     return (out[0, 0], out[1, 0], out[2, 0]) if single else (out[0], out[1], out[2])
