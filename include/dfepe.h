@@ -1337,6 +1337,56 @@ int dfepe_epi_loss_fwd(void *stream, int kind, const float *F, const float *X, c
 int dfepe_epi_loss_bwd(void *stream, int kind, const float *F, const float *X, const float *Y, const float *w, int B, int N,
                        float clamp_at, float eps, const float *g_sum, float *g_F, float *g_X, float *g_Y, float *g_w, void *workspace);
 
+/*
+ * DSAC: the hypothesis loop of deepFEPE/dsac_tools/dsac.py (class DSAC, :138-176, :194) for B pairs and H hypotheses each, in six
+ * launches whatever B and H are (csrc/dsac.hip, csrc/dsac_math.h).  The reference runs it on the CPU, one hypothesis at a time
+ * ("working on CPU because of many, small matrices", :110).  fp32 in and out, fp64 inside, every output rounded once.  No atomics,
+ * no allocation, no host synchronisation: the call can be captured in a hipGraph (one linear chain of launches), and a pair's
+ * outputs are the same bits on every run and whatever else is in the batch.  dfepe_version() stays 154 with this addition: the
+ * number is pinned by existing tests, and nothing that existed changes.
+ *
+ *   X, Y [B,N,2] pixel points, 8-byte aligned; K [B,9]
+ *   idx  [B,H,S] int32: the S correspondences sampled for each hypothesis (random.sample(range(N), 10), :46: S = 10), 8 <= S <= 16,
+ *        N >= S.  Contract, not checked on the device: 0 <= idx < N, and the indices of one hypothesis are distinct.  (An index
+ *        outside 0..N-1 is clamped into the pair by the sample fit and matches no correspondence in the vote.)
+ *   loss_kind  0: none (loss = 0).  1: HLoss(E_refit, X, Y), the mean Sampson distance of the PIXEL points under E_refit itself,
+ *        as :157 with H_loss.py:28 computes it.  2: the same under F = K^-T E_refit K^-1.
+ * Stages:
+ *   1 sample fit (:37-52)   E_sample [B,H,9] = _E_from_XY of the S sampled correspondences: K^-1 points with _de_homo's 1e-10 guard
+ *     (utils_F.py:111-112, rounded to fp32), then dfepe_w8pt_fwd with DFEPE_W8PT_SQRT2 | NO_ROWNORM | FORCE_110 on B H problems.
+ *   2 soft inlier count (:56-76)   F = K^-T E_sample K^-1 (utils_F._E_to_F; the reference names an undefined E_to_F) from the fp32
+ *     E_sample, d = _sampson_dist(F, X, Y) on the pixel points, soft = 1 / (1 + exp(beta (d - thresh))) (= 1 - sigmoid(.), :72),
+ *     score = sum_n soft in fp64 in a fixed order (lane l adds n = l, l + 64, ...; the 64 partial sums by a balanced tree).
+ *     sampson, soft [B,H,N] (each may be NULL), score [B,H].
+ *   3 refit (:78-92, :150)  E_refit [B,H,9] = _E_from_XY of all N correspondences with the row weights sqrt(soft), soft as written
+ *     (fp32); the Hartley transforms are unweighted.  dfepe_w8pt_fwd with n_weight_sets = H.
+ *   4 loss (:157)           loss [B,H] according to loss_kind, from the fp32 E_refit, summed in the order of stage 2.
+ *   5 vote (:163-175, :194) counts [B,N] (float32) = the number of hypotheses that sampled the correspondence, quality [B,N] =
+ *     N_scores / (N_counts + 1e-10) in float32, N_scores = the float32 scores added in hypothesis order: bit-identical to the
+ *     reference's sequential `+=` given the scores.  best [B] int32 = the first hypothesis whose score is the strict maximum above
+ *     0 (:130, :168), -1 when no score is above 0 (a NaN score is never above).  The step the reference leaves commented out
+ *     (:178-190): exp_loss [B] = sum_h softmax(alpha score)_h loss_h, top_loss [B] = loss[best] (0 when best = -1); each may be NULL.
+ * The sign of E_sample and E_refit is dfepe_w8pt_fwd's gauge; every other output is sign-invariant.  A non-finite input stays in its
+ * own pair.
+ *   workspace: dfepe_dsac_workspace_bytes(B, N, H, S) bytes, 16-byte aligned, contents irrelevant (the K^-1 points, the gathered
+ *     samples, the refit's weights [H,B,N], the residuals the fits write, E_refit as the fit lays it out [H,B,9]).
+ *   dfepe_dsac_hyps_per_block(): hypotheses of one pair per workgroup in launches 3 and 5 (a wavefront each);
+ *   dfepe_dsac_vote_chunk(): consecutive correspondences of one pair per workgroup in the vote;
+ *   dfepe_dsac_vote_tile(): hypotheses whose index lists that workgroup stages in LDS at a time.
+ * Refusals, made on the host before any HIP call, in this order: B or N < 0, H < 1, S outside 8..16, N < S, loss_kind outside 0..2:
+ * INVALID_ARG.  Then B == 0 returns OK: nothing is launched and nothing written.  A NULL X, Y, K, idx, E_sample, score, E_refit,
+ * loss, quality, counts, best or workspace; X or Y not 8-byte aligned; a workspace that is not 16-byte aligned: INVALID_ARG.
+ * B * H * N > 2^31 - 1: UNSUPPORTED.  Not built: the adjoint, a device-side sampler, losses other than the two above.
+ */
+int dfepe_dsac_hyps_per_block(void);
+int dfepe_dsac_vote_chunk(void);
+int dfepe_dsac_vote_tile(void);
+size_t dfepe_dsac_workspace_bytes(int B, int N, int H, int S);
+int dfepe_dsac(void *stream, const float *X, const float *Y, const float *K, const int *idx, int B, int N, int H, int S,
+               float inlier_thresh, float inlier_beta, float inlier_alpha, int loss_kind, float *E_sample, float *soft, float *sampson,
+               float *score, float *E_refit, float *loss, float *quality, float *counts, int *best, float *exp_loss, float *top_loss,
+               void *workspace);
+
 #ifdef __cplusplus
 }
 #endif

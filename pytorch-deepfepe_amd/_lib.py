@@ -44,6 +44,7 @@ DETECTOR_EVAL_MAX_N = 4096  # dfepe_keypoint_repeatability (points per image), d
 SP_MAX_PIXELS = 1 << 24  # dfepe_sp_*: pixels per image (sp::kMaxPixels, csrc/sp_process_math.h)
 SP_LDS_PIXELS = 12288  # dfepe_sp_nms: pixels per image up to which no workspace is needed (sp::kLdsPixels)
 SP_MAX_PATCH = 63  # dfepe_sp_soft_argmax: largest patch_size (sp::kMaxPatch)
+DSAC_MIN_SAMPLE, DSAC_MAX_SAMPLE = 8, 16  # dfepe_dsac: correspondences per hypothesis (ds::kMinSample, ds::kMaxSample)
 INLIER_TABLE_MAX_THDS = 16  # dfepe_inlier_table: inlier thresholds per call, and mask thresholds per call (ce::kMaxThds)
 
 _P = c_void_p
@@ -166,6 +167,11 @@ _SIGNATURES = {
     "dfepe_epi_residual_bwd_pts": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, _P, _P, _P]),
     "dfepe_epi_loss_fwd": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P]),
     "dfepe_epi_loss_bwd": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "dfepe_dsac_hyps_per_block": (c_int, []),
+    "dfepe_dsac_vote_chunk": (c_int, []),
+    "dfepe_dsac_vote_tile": (c_int, []),
+    "dfepe_dsac_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dfepe_dsac": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int] + [_P] * 12),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -3,18 +3,36 @@
 The reference runs the loop on the CPU, one hypothesis at a time ("working on CPU because of many, small matrices",
 dsac.py:110): sample 10 correspondences -> _E_from_XY -> soft inlier count from Sampson distances -> refinement by a
 weighted _E_from_XY over all correspondences -> loss, and returns the per-correspondence average score of the hypotheses
-each correspondence was sampled into (:197).  Here the `hyps` hypotheses are independent problems of the same kernels the
-solver uses, so each stage is ONE launch over all hypotheses: the minimal-sample fits (ops.eight_point, B = hyps, N = 10),
-the Sampson distances (ops.epi_metrics, hyps x N lanes), the weighted refinement fits (ops.eight_point, B = hyps, N = N).
-Sampling uses Python's `random.sample` with the reference's call sequence (one call per hypothesis), so a seeded run draws
-the same minimal sets.  The reference calls an undefined `utils_F.E_to_F` at :68 (only `_E_to_F` exists); its evident intent,
-F = K^-T E K^-1, is what is computed.
+each correspondence was sampled into (:194).  Here the whole loop is ops.dsac (dfepe_dsac, include/dfepe.h): every pair of a
+batch and all its hypotheses go through six launches, without a host synchronisation in between.  Sampling uses Python's
+`random.sample` with the reference's call sequence (one call per hypothesis), so a seeded run draws the same minimal sets.
+The reference calls an undefined `utils_F.E_to_F` at :67 (only `_E_to_F` exists); its evident intent, F = K^-T E K^-1, is
+what is computed.  Its prints are not mirrored.
+
+Not built: the adjoint (inputs that require grad raise NotImplementedError), a device-side sampler, and `loss_function`s
+other than H_loss.HLoss on the fused path: any other callable is evaluated per hypothesis on the refitted E, one call and
+its launches per hypothesis -- the slow route.
 """
 import random
 
 import torch
 
-from .. import _lib, ops
+from .. import ops
+from .H_loss import HLoss
+
+SAMPLE = 10  # correspondences per hypothesis (dsac.py:46)
+
+
+def _device_of(*ts):
+    for t in ts:
+        if torch.is_tensor(t) and t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _draw(N, hyps, sample, rng=random):
+    """One random.sample per hypothesis, in hypothesis order (dsac.py:46, :138): raises ValueError when N < sample, as it does."""
+    return [rng.sample(range(N), sample) for _ in range(hyps)]
 
 
 class DSAC:
@@ -26,47 +44,58 @@ class DSAC:
         self.loss_function = loss_function
         self.K = K
 
-    def _normalized(self, P, Ki):
-        """K^-1 applied to inhomogeneous points, _de_homo's 1e-10 guard included (utils_F.py:111-112)."""
-        Ph = torch.cat((P, torch.ones(*P.shape[:-1], 1, device=P.device)), -1) @ Ki.t()
-        return Ph[..., :2] / (Ph[..., 2:3] + 1e-10)
-
     def __call__(self, X, Y, H_gt=None):
-        """X, Y [N,2] pixel correspondences -> [N,1] average soft-inlier score of the hypotheses each correspondence was
-        drawn into (dsac.py:197).  Also sets best_H, best_H_idx, best_dists, best_corres_idx, max_score, inlier_scores
-        [hyps,N], sampson_dists [hyps,N] like the reference."""
-        if not (torch.is_tensor(X) and X.is_cuda):
-            raise _lib.DfepeError("compat.dsac.DSAC: X, Y must live on the GPU (this mirror has no CPU loop)")
-        X, Y = X.float(), Y.float()
-        dev = X.device
+        """X, Y [N,2] pixel correspondences (CPU or GPU) -> [N,1] float32 CPU tensor: the average soft-inlier score of the
+        hypotheses each correspondence was drawn into (dsac.py:194).  Sets inlier_scores [hyps,N], sampson_dists [hyps,N],
+        max_score, best_H, best_H_idx, best_dists, best_corres_idx like the reference (the tensors stay on the device), and
+        hyp_scores, hyp_losses [hyps], exp_loss, top_loss (the step the reference leaves commented out, :178-190)."""
+        X, Y = torch.as_tensor(X), torch.as_tensor(Y)
         N, H = X.shape[0], self.hyps
         assert Y.shape[0] == N, "N mismatch between X and Y!"
+        if any(torch.is_tensor(t) and t.requires_grad for t in (X, Y, self.K)):
+            raise NotImplementedError("compat.dsac.DSAC: the adjoint of the hypothesis loop is not built; detach the inputs")
         self.N = N
-        K = torch.as_tensor(self.K, dtype=torch.float32, device=dev)
-        Ki = torch.linalg.inv(K)
-        idx = torch.tensor([random.sample(range(N), 10) for _ in range(H)], device=dev)  # one draw per hypothesis (:45)
-        Xn, Yn = self._normalized(X, Ki), self._normalized(Y, Ki)
-        # step 1: minimal-sample hypotheses, all at once
-        E = ops.eight_point(Xn[idx].contiguous(), Yn[idx].contiguous(), None, essential=True)          # [H,3,3]
-        # step 2: soft inlier count from the Sampson distances in pixel space
-        F = Ki.t() @ E @ Ki
-        Xe, Ye = X.unsqueeze(0).expand(H, N, 2).contiguous(), Y.unsqueeze(0).expand(H, N, 2).contiguous()
-        d_s = ops.epi_metrics(1, F.contiguous(), Xe, Ye)                                                # [H,N]
-        dists = 1.0 - torch.sigmoid(self.inlier_beta * (d_s - self.inlier_thresh))
-        score = dists.sum(1)
-        # step 3: refinement, weighted fit over all correspondences with W = diag(sqrt(dists)) (:92)
-        Href = ops.eight_point(Xn.unsqueeze(0).expand(H, N, 2).contiguous(), Yn.unsqueeze(0).expand(H, N, 2).contiguous(),
-                               torch.sqrt(dists).contiguous(), essential=True)
-        self.inlier_scores, self.sampson_dists = dists, d_s
-        # step 4: loss of every hypothesis (a user callable, like the reference's)
+        idx_list = _draw(N, H, SAMPLE)
+        dev = _device_of(X, Y)
+        X, Y = X.to(dev, torch.float32), Y.to(dev, torch.float32)
+        K = torch.as_tensor(self.K, dtype=torch.float32).to(dev)
+        fused = isinstance(self.loss_function, HLoss)
+        idx = torch.tensor(idx_list, dtype=torch.int32).to(dev)
+        r = ops.dsac(X[None], Y[None], K.reshape(1, 3, 3), idx[None], self.inlier_thresh, self.inlier_beta, self.inlier_alpha,
+                     loss_kind=1 if fused else 0)
+        self.inlier_scores, self.sampson_dists = r["soft"][0], r["sampson"][0]
+        self.hyp_scores, E_refit = r["score"][0], r["E_refit"][0]
         self.hyp_losses = None
-        if self.loss_function is not None:
-            self.hyp_losses = torch.stack([torch.as_tensor(self.loss_function(Href[h], X, Y), dtype=torch.float32, device=dev).reshape(())
+        self.exp_loss = self.top_loss = None
+        if fused:
+            self.hyp_losses, self.exp_loss, self.top_loss = r["loss"][0], r["exp_loss"][0], r["top_loss"][0]
+        elif self.loss_function is not None:  # the slow route: one call of the user's function per hypothesis (dsac.py:157)
+            self.hyp_losses = torch.stack([torch.as_tensor(self.loss_function(E_refit[h], X, Y), dtype=torch.float32, device=dev).reshape(())
                                            for h in range(H)])
-        self.hyp_scores = score
-        best = int(torch.argmax(score).item())  # first maximum = the reference's strict '>' update (:168)
-        self.max_score = float(score[best].item())
-        self.best_H, self.best_H_idx, self.best_dists, self.best_corres_idx = Href[best], best, dists[best], idx[best].tolist()
-        n_scores = torch.zeros(N, device=dev).index_add_(0, idx.reshape(-1), score.repeat_interleave(10))
-        n_counts = torch.zeros(N, device=dev).index_add_(0, idx.reshape(-1), torch.ones(H * 10, device=dev))
-        return (n_scores / (n_counts + 1e-10)).unsqueeze(1)
+        best = int(r["best"][0].item())  # the one host synchronisation of the call
+        self.max_score = 0
+        if best >= 0:  # the reference leaves these unset when no score is above 0 (:168)
+            self.max_score = float(self.hyp_scores[best].item())
+            self.best_H, self.best_H_idx, self.best_dists = E_refit[best], best, self.inlier_scores[best]
+            self.best_corres_idx = idx_list[best]
+        return r["quality"][0].unsqueeze(1).cpu()
+
+
+def dsac_batch(X, Y, K, hyps, inlier_thresh, inlier_beta, inlier_alpha=0.0, idx=None, seed=None, sample=SAMPLE, loss_kind=0,
+               want=("soft", "sampson", "exp_loss", "top_loss")):
+    """The loop for a batch on the device: X, Y [B,N,2], K [B,3,3] (or [3,3], shared) -> ops.dsac's dict (E_sample, score, E_refit,
+    loss, quality [B,N], counts, best, and what ``want`` names), plus "idx".  ``idx`` [B,hyps,sample] int32 on the device is used
+    as given; otherwise it is drawn on the host -- random.Random(seed), pair by pair, hypothesis by hypothesis, random.sample as
+    the reference draws -- and copied once.  No host synchronisation after that."""
+    if not (torch.is_tensor(X) and X.is_cuda):
+        raise ops._lib.DfepeError("compat.dsac.dsac_batch: X, Y must live on the GPU (this package has no CPU path)")
+    B, N = X.shape[0], X.shape[1]
+    K = torch.as_tensor(K, dtype=torch.float32).to(X.device)
+    if K.dim() == 2:
+        K = K.expand(B, 3, 3)
+    if idx is None:
+        rng = random.Random(seed)
+        idx = torch.tensor([_draw(N, hyps, sample, rng) for _ in range(B)], dtype=torch.int32).reshape(B, hyps, sample).to(X.device)
+    out = ops.dsac(X, Y, K.contiguous(), idx, inlier_thresh, inlier_beta, inlier_alpha, loss_kind=loss_kind, want=want)
+    out["idx"] = idx
+    return out

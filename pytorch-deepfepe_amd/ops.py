@@ -2207,3 +2207,56 @@ def inlier_table_mean(ratio: Tensor, num: Tensor):
         rc = _lib.lib().dfepe_inlier_table_mean(_ptr(r), _ptr(n), B, Tm, Ti, _ptr(mean), _ptr(num_T), _stream())
     _lib.check(rc, "dfepe_inlier_table_mean")
     return mean, num_T
+
+
+# ------------------------------------------------------------------------------------------------
+# DSAC: the hypothesis loop of dsac_tools/dsac.py, batched over pairs and hypotheses
+# ------------------------------------------------------------------------------------------------
+DSAC_LOSS_KINDS = {None: 0, "none": 0, "hloss": 1, "hloss_F": 2}
+
+
+def dsac(X: Tensor, Y: Tensor, K: Tensor, idx: Tensor, inlier_thresh: float, inlier_beta: float, inlier_alpha: float = 0.0,
+         loss_kind=0, want=("soft", "sampson", "exp_loss", "top_loss")) -> dict:
+    """The DSAC loop of deepFEPE/dsac_tools/dsac.py (:138-176, :194) for B pairs and H hypotheses each in six launches:
+    X, Y [B,N,2] pixel points, K [B,3,3], idx [B,H,S] int32 on the device (8 <= S <= 16, N >= S; distinct within a hypothesis and
+    0 <= idx < N: a contract) -> dict with E_sample [B,H,3,3], score [B,H], E_refit [B,H,3,3], loss [B,H], quality [B,N], counts
+    [B,N], best [B] int32 and, as named in ``want``, soft [B,H,N], sampson [B,H,N], exp_loss [B], top_loss [B].
+    ``loss_kind``: 0 / "none", 1 / "hloss" (HLoss(E_refit, X, Y) as the reference calls it), 2 / "hloss_F" (under K^-T E_refit K^-1).
+    include/dfepe.h (dfepe_dsac) has the contract.  No host synchronisation and no allocation inside the call; capturable."""
+    X, Y, K = _prep(X, "X"), _prep(Y, "Y"), _prep(K, "K")
+    if not torch.is_tensor(idx) or not idx.is_cuda:
+        raise _lib.DfepeError("idx must live on the GPU (this package has no CPU path)")
+    _shape(X, "X", None, None, 2)
+    B, N = X.shape[0], X.shape[1]
+    _shape(Y, "Y", B, N, 2)
+    _shape(K, "K", B, 3, 3)
+    _shape(idx, "idx", B, None, None)
+    H, S = idx.shape[1], idx.shape[2]
+    if not _lib.DSAC_MIN_SAMPLE <= S <= _lib.DSAC_MAX_SAMPLE or N < S or H < 1:
+        raise ValueError(f"dsac: idx [B,H,S] needs H >= 1 and {_lib.DSAC_MIN_SAMPLE} <= S <= {_lib.DSAC_MAX_SAMPLE} <= N, got H={H}, S={S}, N={N}")
+    kind = DSAC_LOSS_KINDS.get(loss_kind, loss_kind) if isinstance(loss_kind, (str, type(None))) else int(loss_kind)
+    if kind not in (0, 1, 2):
+        raise ValueError(f"dsac: loss_kind must be 0, 1, 2 or one of {[k for k in DSAC_LOSS_KINDS if k]}, got {loss_kind!r}")
+    want = tuple(want)
+    if any(w not in ("soft", "sampson", "exp_loss", "top_loss") for w in want):
+        raise ValueError(f"dsac: want names soft, sampson, exp_loss, top_loss; got {want}")
+    idx = idx.to(torch.int32).contiguous()
+    dev = X.device
+    L = _lib.lib()
+
+    def f32(*shape, name=None):
+        return torch.empty(*shape, device=dev, dtype=torch.float32) if name is None or name in want else None
+
+    out = {"E_sample": f32(B, H, 3, 3), "soft": f32(B, H, N, name="soft"), "sampson": f32(B, H, N, name="sampson"), "score": f32(B, H),
+           "E_refit": f32(B, H, 3, 3), "loss": f32(B, H), "quality": f32(B, N), "counts": f32(B, N),
+           "best": torch.empty(B, device=dev, dtype=torch.int32), "exp_loss": f32(B, name="exp_loss"), "top_loss": f32(B, name="top_loss")}
+    if B == 0:
+        return {k: v for k, v in out.items() if v is not None}
+    ws = torch.empty(L.dfepe_dsac_workspace_bytes(B, N, H, S) // 4, device=dev, dtype=torch.float32)
+    with _on(dev):
+        rc = L.dfepe_dsac(_stream(), _ptr(X), _ptr(Y), _ptr(K), _ptr(idx), B, N, H, S, float(inlier_thresh), float(inlier_beta),
+                          float(inlier_alpha), kind, _ptr(out["E_sample"]), _ptr(out["soft"]), _ptr(out["sampson"]), _ptr(out["score"]),
+                          _ptr(out["E_refit"]), _ptr(out["loss"]), _ptr(out["quality"]), _ptr(out["counts"]), _ptr(out["best"]),
+                          _ptr(out["exp_loss"]), _ptr(out["top_loss"]), _ptr(ws))
+    _lib.check(rc, "dfepe_dsac")
+    return {k: v for k, v in out.items() if v is not None}
