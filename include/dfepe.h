@@ -44,7 +44,7 @@ extern "C" {
 #define DFEPE_W8PT_LOGITS 2u      /* `weights` holds logits [B,N]; softmax over N (F.softmax(logits, dim=2),
                                      DeepFNet.py:443,512) is fused in and the weights are written to `weights_out`;
                                      the backward then returns the gradient w.r.t. the logits                */
-/* variants of the textbook normalised 8-point solvers of dsac_tools (forward only):                         */
+/* variants of the textbook normalised 8-point solvers of dsac_tools (adjoint: dfepe_eight_point_bwd):       */
 #define DFEPE_W8PT_SQRT2 4u       /* Hartley scale sqrt(2) (utils_F._normalize_XY, utils_F.py:23) instead of the
                                      literal 1.4142 of Fit.normalize                                         */
 #define DFEPE_W8PT_NO_ROWNORM 8u  /* rows of the design matrix are not normalised to unit length
@@ -1376,7 +1376,8 @@ int dfepe_epi_loss_bwd(void *stream, int kind, const float *F, const float *X, c
  * Refusals, made on the host before any HIP call, in this order: B or N < 0, H < 1, S outside 8..16, N < S, loss_kind outside 0..2:
  * INVALID_ARG.  Then B == 0 returns OK: nothing is launched and nothing written.  A NULL X, Y, K, idx, E_sample, score, E_refit,
  * loss, quality, counts, best or workspace; X or Y not 8-byte aligned; a workspace that is not 16-byte aligned: INVALID_ARG.
- * B * H * N > 2^31 - 1: UNSUPPORTED.  Not built: the adjoint, a device-side sampler, losses other than the two above.
+ * B * H * N > 2^31 - 1: UNSUPPORTED.  Not built: the adjoint of the loop (the adjoint of its two fits exists: dfepe_eight_point_bwd
+ * below), a device-side sampler, losses other than the two above.
  */
 int dfepe_dsac_hyps_per_block(void);
 int dfepe_dsac_vote_chunk(void);
@@ -1386,6 +1387,58 @@ int dfepe_dsac(void *stream, const float *X, const float *Y, const float *K, con
                float inlier_thresh, float inlier_beta, float inlier_alpha, int loss_kind, float *E_sample, float *soft, float *sampson,
                float *score, float *E_refit, float *loss, float *quality, float *counts, int *best, float *exp_loss, float *top_loss,
                void *workspace);
+
+/*
+ * Adjoint of the textbook normalised eight-point solvers: utils_F._F_from_XY (deepFEPE/dsac_tools/utils_F.py:223-275), _E_from_XY
+ * (:104-155) and _E_from_XY_batch (:157-221), i.e. of dfepe_w8pt_fwd with DFEPE_W8PT_SQRT2 | DFEPE_W8PT_NO_ROWNORM, which
+ * dfepe_w8pt_bwd refuses (csrc/eight_point_adjoint.hip, csrc/eight_point_adjoint_math.h).  Gradients to the points and the weights.
+ * fp32 in and out, fp64 inside, every output rounded once.  Nothing is saved by the forward: the fit is recomputed.  No atomics, no
+ * allocation, no host synchronisation: the call (at most two launches) can be captured in a hipGraph, and a problem's outputs are the
+ * same bits on every run and whatever else is in the batch.  A non-finite input stays in its own pair.  dfepe_version() stays 154 with
+ * this addition: the number is pinned by existing tests, and nothing that existed changes.
+ *
+ *   X, Y   [B,N,2]  the 2-D points the forward saw (its third coordinate was 1), 8-byte aligned; N >= 8
+ *   w      [S,B,N]  or NULL (= 1); S = n_weight_sets >= 1, the forward's layout
+ *   flags  must contain DFEPE_W8PT_SQRT2 | DFEPE_W8PT_NO_ROWNORM; DFEPE_W8PT_FORCE_110 and DFEPE_W8PT_NO_HARTLEY are optional
+ *   F_out  [S,B,9]  the forward's output: only its sign is read, the recomputed matrix is oriented to it by their inner product
+ *   g_F    [S,B,9]  the gradient w.r.t. F_out as given
+ *   g_X, g_Y [B,N,2] (8-byte aligned), g_w [S,B,N]: written, not accumulated; each may be NULL and is then skipped, not all three.
+ *          With S > 1, g_X[b,n] and g_Y[b,n] are the sums over the weight sets, added in set order in fp64.
+ *   workspace  dfepe_eight_point_bwd_workspace_bytes(B, N, S) bytes, 16-byte aligned, contents irrelevant; 0 bytes (NULL allowed)
+ *          when S == 1; only touched when S > 1 and g_X or g_Y is asked for.
+ *
+ * Per problem (pair b, weight set s), with p~ the normalised points (c = mean p, scale = sqrt(2) / mean |p - c|,
+ * p~ = scale (p - c) / (1 + 1e-10), T = [[scale,0,-scale cx],[0,scale,-scale cy],[0,0,1]]; p~ = p, T = I with NO_HARTLEY):
+ *   a_i = [x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1], A_i = w_i a_i, M9 = A^T A = sum lam_k q_k q_k^T, f = q_9 (smallest),
+ *   F0 = reshape(f) = U diag(s1,s2,s3) V^T, M = U diag(s1,s2,0) V^T (FORCE_110: diag(1,1,0)), out = T2^T M T1.
+ * T1 and T2 are CONSTANTS in the adjoint: the reference builds them with torch.tensor([[S1, 0, ...]]) (utils_F.py:25,35, and :52,65
+ * in the batch form), which detaches them, so the reference's own gradient never passes through the centroid or the scale.
+ *   G = T2 g_F T1^T, G^ = U^T G V, g_F0 = U P V^T, d_k = s_k^2 - s3^2 (k = 1, 2):
+ *     without FORCE_110 (M = F0 - s3 u3 v3^T):  P = G^ except P_33 = 0, P_k3 = G^_k3 + s3 (s3 G^_k3 + s_k G^_3k) / d_k,
+ *                                               P_3k = G^_3k + s3 (s_k G^_k3 + s3 G^_3k) / d_k
+ *     with FORCE_110:  P = 0 except P_12 = -P_21 = (G^_12 - G^_21) / (s1 + s2), P_k3 = (s_k G^_k3 + s3 G^_3k) / d_k,
+ *                      P_3k = (s3 G^_k3 + s_k G^_3k) / d_k.  Nothing divides by s1 - s2: the gradient is finite at an exact
+ *                      essential matrix (s1 = s2), where torch's svd_backward is singular.
+ *   u = sum_{k != 9} q_k (q_k^T vec(g_F0)) / (lam_9 - lam_k);  r_i = A_i . f, g_A_i = r_i u + (A_i . u) f, g_w_i = a_i . g_A_i,
+ *   g_a_i = w_i g_A_i, to p~ by the product rule, and g_p = scale / (1 + 1e-10) g_p~.
+ *   With N = 8 the eight rows have an exact null vector: A f = 0 whatever the points and weights are, so r_i is taken as the
+ *   constant 0 it is (not the rounding noise A_i . f evaluates to) and g_w is written as 0.
+ * Guard rule: every denominator above (lam_9 - lam_k, s_k^2 - s3^2, s1 + s2), and the s1, s2 that normalise u1, u2, keeps its sign and has its magnitude floored at 1e-30
+ * (guard_den16 of the fit adjoint): a repeated eigen- or singular value gives a large finite gradient, not a NaN.
+ *
+ * Launch shape: one wavefront per problem, four problems per workgroup; with S > 1 and point gradients asked for, a second launch
+ * adds the sets' partial gradients [S,B,N,4] (fp64, in the workspace) in ascending set order.
+ *
+ * Refusals, made on the host before any HIP call, in this order: B < 0, N < 8 or n_weight_sets < 1: INVALID_ARG.  `flags` without
+ * SQRT2 | NO_ROWNORM, or with a bit other than those two, FORCE_110 and NO_HARTLEY: INVALID_ARG.  Then B == 0 returns OK: nothing
+ * is launched and nothing written.  A NULL X, Y, F_out or g_F, or g_X, g_Y and g_w all NULL: INVALID_ARG.  X, Y, g_X or g_Y not
+ * 8-byte aligned: INVALID_ARG.  S > 1 with g_X or g_Y asked for and a NULL workspace or one not 16-byte aligned: INVALID_ARG.
+ * S * B * N > 2^31 - 1: UNSUPPORTED.
+ */
+size_t dfepe_eight_point_bwd_workspace_bytes(int B, int N, int n_weight_sets);
+int dfepe_eight_point_bwd(void *stream, const float *X, const float *Y, const float *w, int B, int N, int n_weight_sets,
+                          unsigned flags, const float *F_out, const float *g_F,
+                          float *g_X, float *g_Y, float *g_w, void *workspace);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ batch and all its hypotheses go through six launches, without a host synchronisa
 The reference calls an undefined `utils_F.E_to_F` at :67 (only `_E_to_F` exists); its evident intent, F = K^-T E K^-1, is
 what is computed.  Its prints are not mirrored.
 
-Not built: the adjoint (inputs that require grad raise NotImplementedError), a device-side sampler, and `loss_function`s
+Not built: the adjoint of the loop (inputs that require grad raise NotImplementedError; the adjoint of its two fits exists,
+ops.eight_point / dfepe_eight_point_bwd, the loop's own is what is missing), a device-side sampler, and `loss_function`s
 other than H_loss.HLoss on the fused path: any other callable is evaluated per hypothesis on the refitted E, one call and
 its launches per hypothesis -- the slow route.
 """

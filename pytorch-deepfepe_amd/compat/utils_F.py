@@ -274,6 +274,26 @@ def _diag_weights(W, N):
     return torch.diagonal(W) if float(off.abs().max()) == 0.0 else None
 
 
+def _solve(X, Y, W, essential, normalize):
+    """The solve of _F_from_XY / _E_from_XY on prepared points, and where it runs.  The fit kernel has its adjoint (ops.eight_point:
+    dfepe_eight_point_bwd), to the points and to a weight VECTOR: W None, 1-D (with or without a gradient of its own) or a diagonal
+    [N,N] matrix that does not itself require grad stay on the kernel, asked for gradients or not.  A 2-D W that requires grad has
+    off-diagonal gradients in the reference which the kernel does not have, and a dense W mixes correspondences: asked for
+    gradients, those two go through the torch expression of _autograd_paths.eight_point (whose Hartley derivative is not the
+    reference's); a dense W without a gradient request is _dense_w_solve.  The diagonal test (one [N,N] temporary and
+    one host synchronisation) is made once."""
+    grad = _ap.wants_grad(X, Y, W)
+    w = None
+    if W is not None:
+        W = _gpu(W)
+        if grad and W.dim() == 2 and W.requires_grad:
+            return _ap.eight_point(X, Y, W, essential=essential, normalize=normalize)
+        w = _diag_weights(W, X.shape[0])
+        if w is None:
+            return _ap.eight_point(X, Y, W, essential=essential, normalize=normalize) if grad else _dense_w_solve(X, Y, W, essential, normalize)
+    return ops.eight_point(X.unsqueeze(0), Y.unsqueeze(0), None if w is None else w.unsqueeze(0), essential=essential, normalize=normalize)[0]
+
+
 def _dense_w_solve(X, Y, W, essential, normalize):
     """Dense W [N,N] (utils_F.py:129-130,245-246): rows of W @ XX are mixtures of correspondences, so the design matrix is formed
     explicitly (elementwise plumbing + one [N,N]x[N,9] product) and handed to the explicit-rows closing kernel
@@ -288,21 +308,20 @@ def _dense_w_solve(X, Y, W, essential, normalize):
 
 
 def _F_from_XY(X, Y, W=None, normalize=True, show_debug=False):
-    """Normalised 8-point fundamental matrix from X, Y [N,2] (utils_F.py:223-275); sign follows this library's gauge (with inputs
-    that require grad: torch.linalg.svd's, through the differentiable evaluation of _autograd_paths)."""
-    X, Y = _gpu(X), _gpu(Y)
-    if _ap.wants_grad(X, Y, W):
-        return _ap.eight_point(X, Y, None if W is None else _gpu(W), essential=False, normalize=normalize)
-    w = None if W is None else _diag_weights(W, X.shape[0])
-    if W is not None and w is None:
-        return _dense_w_solve(X, Y, W, False, normalize)
-    return ops.eight_point(X.unsqueeze(0), Y.unsqueeze(0), None if w is None else w.unsqueeze(0), essential=False, normalize=normalize)[0]
+    """Normalised 8-point fundamental matrix from X, Y [N,2] (utils_F.py:223-275); sign follows this library's gauge.
+    Differentiable in X, Y and a weight vector through the kernel's own adjoint (ops.eight_point), with the Hartley transforms
+    constant as in the reference (:25,35); a W [N,N] that requires grad, or a dense one, takes the torch route (_solve)."""
+    return _solve(_gpu(X), _gpu(Y), W, False, normalize)
 
 
 def _E_from_XY_batch(X, Y, K, W=None, if_normzliedK=False, normalize=True, show_debug=False):
     """Batched _E_from_XY (utils_F.py:157-221): X, Y [B,N,2], K [B,3,3]; like the reference it returns the NEGATED matrix
-    (:221).  W: per-correspondence weights [B,N] (the reference takes dense [B,N,N] matrices; only diagonals are built)."""
+    (:221).  W: per-correspondence weights [B,N] (the reference takes dense [B,N,N] matrices; only diagonals are built).
+    Differentiable in X, Y, K and W [B,N] (ops.eight_point's adjoint; the K^-1 step is the torch expression in front of it).  A
+    [B,N,N] W that requires grad is refused: its off-diagonal gradient exists in the reference and is not built here."""
     X, Y = _gpu(X), _gpu(Y)
+    if W is not None and torch.is_tensor(W) and W.dim() == 3 and _ap.wants_grad(W):
+        raise _lib.DfepeError("_E_from_XY_batch: a [B,N,N] W that requires grad is not built (pass the weights as [B,N])")
     if not if_normzliedK:
         Ki = torch.linalg.inv(_gpu(K))
         ones = torch.ones(X.shape[0], X.shape[1], 1, device=X.device)
@@ -316,16 +335,12 @@ def _E_from_XY_batch(X, Y, K, W=None, if_normzliedK=False, normalize=True, show_
 
 
 def _E_from_XY(X, Y, K, W=None, if_normzliedK=False, normalize=True, show_debug=False):
-    """Normalised 8-point essential matrix (utils_F.py:104-155): K^-1 points, sqrt(2) Hartley, singular values (1,1,0)."""
+    """Normalised 8-point essential matrix (utils_F.py:104-155): K^-1 points, sqrt(2) Hartley, singular values (1,1,0).
+    Differentiable like _F_from_XY, and in K through the K^-1 step, a torch expression in front of the kernel."""
     X, Y = _gpu(X), _gpu(Y)
     if not if_normzliedK:
         Ki = torch.linalg.inv(_gpu(K))
         ones = torch.ones(X.shape[0], 1, device=X.device)
         Xh, Yh = torch.cat((X, ones), 1) @ Ki.t(), torch.cat((Y, ones), 1) @ Ki.t()
         X, Y = Xh[:, :2] / (Xh[:, 2:3] + 1e-10), Yh[:, :2] / (Yh[:, 2:3] + 1e-10)  # _de_homo (utils_misc.py:69-78)
-    if _ap.wants_grad(X, Y, W):  # the reference's own differentiable route (legacy callers, dsac.py:138-176)
-        return _ap.eight_point(X, Y, None if W is None else _gpu(W), essential=True, normalize=normalize)
-    w = None if W is None else _diag_weights(W, X.shape[0])
-    if W is not None and w is None:
-        return _dense_w_solve(X, Y, W, True, normalize)
-    return ops.eight_point(X.unsqueeze(0), Y.unsqueeze(0), None if w is None else w.unsqueeze(0), essential=True, normalize=normalize)[0]
+    return _solve(X, Y, W, True, normalize)

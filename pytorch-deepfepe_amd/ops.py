@@ -236,26 +236,82 @@ def w8pt_backward(pts1, pts2, weights, raw, image_w, image_h, clamp_at, save, F,
     return (gW, gP1, gP2) if want_pts else gW
 
 
-def eight_point(X: Tensor, Y: Tensor, w: Optional[Tensor], essential: bool, normalize: bool = True) -> Tensor:
-    """Textbook normalised 8-point on 2-D points X, Y [B,N,2] with optional per-correspondence weights [B,N]
-    (utils_F._F_from_XY / _E_from_XY after the K^-1 step): sqrt(2) Hartley (none when ``normalize`` is False),
-    unnormalised rows, S3 -> 0 or (1,1,0)."""
-    X, Y = _prep(X, "X"), _prep(Y, "Y")
+def _eight_point_flags(essential: bool, normalize: bool) -> int:
+    return (_lib.W8PT_SQRT2 | _lib.W8PT_NO_ROWNORM | (_lib.W8PT_FORCE_110 if essential else 0) |
+            (0 if normalize else _lib.W8PT_NO_HARTLEY))
+
+
+def _eight_point_launch(X: Tensor, Y: Tensor, w: Optional[Tensor], S: int, essential: bool, normalize: bool) -> Tensor:
+    """The forward fit: X, Y [B,N,2] and w [S,B,N] (None = ones, S = 1), prepared -> F [S,B,3,3]."""
     B, N = X.shape[0], X.shape[1]
     ones = torch.ones(B, N, 1, device=X.device)
     p1 = torch.cat((X, ones), 2).contiguous()
     p2 = torch.cat((Y, ones), 2).contiguous()
-    wt = torch.ones(B, N, device=X.device) if w is None else _prep(w.reshape(B, N), "w")
+    wt = torch.ones(B, N, device=X.device) if w is None else w
     L = _lib.lib()
-    F = torch.empty(B, 3, 3, device=X.device)
-    residual = torch.empty(B, N, device=X.device)
-    flags = (_lib.W8PT_SQRT2 | _lib.W8PT_NO_ROWNORM | (_lib.W8PT_FORCE_110 if essential else 0) |
-             (0 if normalize else _lib.W8PT_NO_HARTLEY))
+    F = torch.empty(S, B, 3, 3, device=X.device)
+    residual = torch.empty(S, B, N, device=X.device)
     with _on(X.device):
-        rc = L.dfepe_w8pt_fwd(_ptr(p1), _ptr(p2), _ptr(wt), B, N, 1, flags, 0.0, 0.0, 0.5, _ptr(F), _ptr(residual), None, None, None,
-                              _stream())
+        rc = L.dfepe_w8pt_fwd(_ptr(p1), _ptr(p2), _ptr(wt), B, N, S, _eight_point_flags(essential, normalize), 0.0, 0.0, 0.5, _ptr(F),
+                              _ptr(residual), None, None, None, _stream())
     _lib.check(rc, "dfepe_w8pt_fwd")
     return F
+
+
+class _EightPointFunction(torch.autograd.Function):
+    """The fit with its adjoint (dfepe_eight_point_bwd: the fit is recomputed in fp64, nothing but the inputs and F is saved)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, w, S, essential, normalize):
+        F = _eight_point_launch(X, Y, w, S, essential, normalize)
+        ctx.save_for_backward(X, Y, w, F)
+        ctx.cfg = (S, essential, normalize)
+        return F
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        X, Y, w, F = ctx.saved_tensors
+        S, essential, normalize = ctx.cfg
+        B, N = X.shape[0], X.shape[1]
+        g = g.contiguous().float()
+        need = ctx.needs_input_grad
+        gX = torch.empty_like(X) if need[0] else None
+        gY = torch.empty_like(Y) if need[1] else None
+        gw = torch.empty_like(w) if (w is not None and need[2]) else None
+        L = _lib.lib()
+        nbytes = int(L.dfepe_eight_point_bwd_workspace_bytes(B, N, S)) if (gX is not None or gY is not None) else 0
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=X.device) if nbytes else None
+        with _on(X.device):
+            rc = L.dfepe_eight_point_bwd(_stream(), _ptr(X), _ptr(Y), _ptr(w), B, N, S, _eight_point_flags(essential, normalize), _ptr(F),
+                                         _ptr(g), _ptr(gX), _ptr(gY), _ptr(gw), _ptr(ws))
+        _lib.check(rc, "dfepe_eight_point_bwd")
+        return gX, gY, gw, None, None, None
+
+
+def eight_point(X: Tensor, Y: Tensor, w: Optional[Tensor], essential: bool, normalize: bool = True) -> Tensor:
+    """Textbook normalised 8-point on 2-D points X, Y [B,N,2] with optional per-correspondence weights [B,N]
+    (utils_F._F_from_XY / _E_from_XY after the K^-1 step): sqrt(2) Hartley (none when ``normalize`` is False),
+    unnormalised rows, S3 -> 0 or (1,1,0).  Returns F [B,3,3].
+    w [S,B,N] with S > 1: S weightings of the same B pairs in one launch; returns [S,B,3,3] (a leading dimension of 1 is the
+    single weighting it always was and returns [B,3,3]).
+    Differentiable w.r.t. X, Y and w (dfepe_eight_point_bwd; with several weightings the point gradients are their sum).  The
+    Hartley transforms are constants of the adjoint, as the reference's own autograd has them (utils_F.py:25,35).  With nothing
+    requiring grad it is the forward launch alone."""
+    X, Y = _prep(X, "X"), _prep(Y, "Y")
+    B, N = X.shape[0], X.shape[1]
+    sets = w is not None and w.dim() == 3 and w.shape[0] > 1 and tuple(w.shape[1:]) == (B, N)
+    S = w.shape[0] if sets else 1
+    wt = None if w is None else _prep(w if sets else w.reshape(B, N), "w").reshape(S, B, N)
+    if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad or (wt is not None and wt.requires_grad)):
+        if X.dim() != 3 or X.shape[2] != 2 or Y.shape != X.shape:
+            raise ValueError(f"eight_point: X and Y [B,N,2] expected, got {tuple(X.shape)}, {tuple(Y.shape)}")
+        # the adjoint reads the points as 8-byte pairs: a contiguous view that starts at an odd element of its buffer is copied
+        X, Y = (t.clone() if t.data_ptr() % 8 else t for t in (X, Y))
+        F = _EightPointFunction.apply(X, Y, wt, S, essential, normalize)
+    else:
+        F = _eight_point_launch(X, Y, wt, S, essential, normalize)
+    return F if sets else F[0]
 
 
 def eight_point_rows(rows: Tensor, T1: Optional[Tensor], T2: Optional[Tensor], essential: bool) -> Tensor:
