@@ -1,7 +1,8 @@
 """The per-correspondence weight estimator on the matrix cores: host side.
 
 ``estimator_forward(x, layers, head)`` evaluates the Conv1d(k=1) -> InstanceNorm1d(affine) -> LeakyReLU stack of
-ErrorEstimator (deepFEPE/models/ErrorEstimators.py:47-64) with the kernels of csrc/est_gemm.hip: every fp32 operand travels as
+ErrorEstimator (deepFEPE/models/ErrorEstimators.py:47-64) with the kernels of csrc/est_*.hip (est_gemm: the products, est_norm: normalisation, adjoints and head, est_planes: plane making
+and reductions, est_pass: one pass per call; est_common.h: what they share): every fp32 operand travels as
 16-bit planes.  Forward (round 5): two fp16 planes per operand (a = a0 + a1 to 22 bits), three MFMAs per product with fp32
 accumulation -- fp32-class accuracy at half the matrix work of the six bf16 products of rounds 3-4; each layer's weights are split
 scaled by a power of two found on the device (dfepe_est_absmax) so that their low plane stays out of fp16's subnormal range.

@@ -1,5 +1,5 @@
 """GPU time of ONE estimator call (forward + backward, captured in a hipGraph and replayed: no host in the figure) for a list of batch sizes, under
-the plan switch of csrc/est_gemm.hip (DFEPE_EST_SPLITK = 0: fused epilogues wherever they exist, never split; 1: the default plan; 2: plain
+the plan switch of csrc/est_pass.hip (DFEPE_EST_SPLITK = 0: fused epilogues wherever they exist, never split; 1: the default plan; 2: plain
 products + register-resident normalisation everywhere).   DFEPE_EST_SPLITK=1 python scripts/est_plan_sweep.py N B1 B2 ..."""
 import importlib, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

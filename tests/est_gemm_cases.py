@@ -1,10 +1,10 @@
-"""The case matrix of the estimator's GEMM kernels (csrc/est_gemm.hip) and one check() per entry point, shared by the host test of
+"""The case matrix of the estimator's GEMM kernels (csrc/est_gemm.hip, constants in csrc/est_common.h) and one check() per entry point, shared by the host test of
 the restatement (tests/test_est_gemm_ref_cpu.py: an fp32 evaluation on host-built planes, and mutations of it) and the device test
 (tests/test_est_gemm_edges_gpu.py).  The reference and every bound are tests/est_gemm_ref.py's.
 
-Launch geometry, restated once from est_gemm.hip (BM = 128 channels and BSTEP = 200 owned columns per workgroup, lines 69-73; the grid
-of every est_gemm_nt_kernel launch, e.g. line 1786; small_grid(), line 1671: the AHEAD = 2 build at up to 256 workgroups, the
-default build above; the XCD remap, line 239: taken when gridDim.x % 8 == 0):
+Launch geometry, restated once from the sources (est_common.h's constants BM = 128 channels and BSTEP = 200 owned columns per
+workgroup; est_gemm.hip: the grid every entry point hands to launch_nt(); small_grid(): the AHEAD = 2 build at up to 256 workgroups,
+the default build above; the XCD remap at the top of est_gemm_nt_kernel: taken when gridDim.x % 8 == 0):
     workgroups(M, ncols, S) = ceil(ncols / 200) * ceil(M / 128) * S
     build    = "small" if workgroups <= 256 else "full"
     remapped = ceil(ncols / 200) % 8 == 0
@@ -146,7 +146,7 @@ def affine(M, g, zero=(5,)):
 
 def layer_fwd_inputs(case):
     """(W [M, K], X [ncols, K], gamma, beta).  One pair (the second, or the only one) is a constant column plus noise of 1e-3 -- its
-    variance is close to eps, the cancellation est_gemm.hip:699 speaks of; the noise is t[col] v[k] with |t| in [0.9, 1.1], so that the pair's normalised
+    variance is close to eps, the cancellation est_gemm_nt_kernel's EPI_IN epilogue speaks of ("the difference first"); the noise is t[col] v[k] with |t| in [0.9, 1.1], so that the pair's normalised
     values stay near +-1 and away from the kink however wide the bound is there.  gamma[5] = 0."""
     _, M, pairs, K, absmax, keep = case
     g = _gen(case)

@@ -2,7 +2,7 @@
 that tests/est_gemm_cases.py holds them to, element by element.  torch float64, no GPU needed (it runs wherever its arguments live).
 
 It works from the PLANES' values -- read back after the device split, or built on the host (host_planes_*) -- in the K-blocked
-layout of est_gemm.hip's kb_index, [planes][C/32][rows][32]: what an operand lost when it was split is not the kernels' error and is
+layout of est_common.h's kb_index, [planes][C/32][rows][32]: what an operand lost when it was split is not the kernels' error and is
 not in the reference; what remains is fp32 accumulation and the epilogues' fp32 arithmetic.
 
 Bounds (u = 2^-24; first order, SLACK = 1 + 2^-10 on every final bound for the second-order terms; each bound is on
@@ -13,7 +13,7 @@ product   The kernel multiplies exactly the terms A_i B_j^T with i + j <= order 
           order, DOUBLED because the matrix core's internal rounding is not specified:  n 2^-23 sum_terms |A_i| |B_j|^T.
           A split-K slice is the same over its own K steps.  The scaled fp16 path divides value and bound by the power-of-two scale
           (exact).
-EPI_IN    est_gemm.hip:661-716, per (pair, channel) over the pair's 100 columns, y = the product, dy its bound:
+EPI_IN    est_gemm_nt_kernel, EPI_IN epilogue, per (pair, channel) over the pair's 100 columns, y = the product, dy its bound:
             mean      99 additions, the rounded 1 / 100, one product:           dmu   = mean(dy) + 101 u mean|y|
             d = y - mu                                                          dd    = dy + dmu + u |d|
             q = sum d^2 (100 fused multiply-adds, one row sum)                  dq    = sum 2 |d| dd + 101 u q
@@ -27,7 +27,7 @@ EPI_IN    est_gemm.hip:661-716, per (pair, channel) over the pair's 100 columns,
           spacing 2^-24), two bf16 planes 2^-16 |a|.
           undecided: |z| <= dz (TOL dz for a slope above one) -- the two LeakyReLU branches differ by less than that there; such an
           element is still compared, with the bound widened by |z|.
-EPI_INBWD est_gemm.hip:494-657.  dA = the product (bound ddA); a = the fp32 sum of the two stored bf16 planes (exact: both sides
+EPI_INBWD est_gemm_nt_kernel, EPI_INBWD epilogue.  dA = the product (bound ddA); a = the fp32 sum of the two stored bf16 planes (exact: both sides
           read the same bits, so the branch is decided except at a == 0, where the bound is widened by |dA| |1 - slope|).
             z = a, or a * fl(1 / slope)                                         dzz   = 0, or 2 u |z|
             e = dz = dA, or dA * slope                                          de    = ddA, or slope ddA + u |e|
@@ -51,8 +51,8 @@ import torch
 U = 2.0 ** -24
 SLACK = 1.0 + 2.0 ** -10
 TOL = 2.0
-KPTS = 100       # est_gemm.hip: kPts
-GAMMA_MIN = 1e-30  # est_gemm.hip:517: below it the adjoint takes x^ = 0
+KPTS = 100       # est_common.h: kPts
+GAMMA_MIN = 1e-30  # the `ig` of the EPI_INBWD epilogue and of est_norm.hip's adjoints: below it they take x^ = 0
 
 
 def unblock(P):
@@ -78,7 +78,7 @@ def host_planes_bf16(x, n_planes):
 
 
 def weight_scale(absmax):
-    """The power of two that brings max |W| into [8, 16) (est_gemm.hip: wscale, exponent clamped like there)."""
+    """The power of two that brings max |W| into [8, 16) (est_common.h: wscale, exponent clamped like there)."""
     eb = int(torch.tensor(float(absmax), dtype=torch.float32).view(torch.int32).item() >> 23) & 255
     return 2.0 ** (130 - min(max(eb, 100), 150))
 
@@ -109,7 +109,7 @@ def product(Ap, Bp, order, scale=1.0, ksteps=None):
 
 
 def split_ksteps(K, S):
-    """The K steps of each of S slices, as est_gemm_nt_kernel divides them (est_gemm.hip:263-264)."""
+    """The K steps of each of S slices, as est_gemm_nt_kernel divides them (its ks_begin and nk)."""
     nk = K // 32
     return [((nk * z) // S, (nk * (z + 1)) // S) for z in range(S)]
 
@@ -151,7 +151,7 @@ def layer_forward(Wp, Xp, scale, gamma, beta, eps, slope):
 
 
 def stored_activation(ap):
-    """a as the adjoint kernels read it: the fp32 sum of the two leading bf16 planes (est_gemm.hip:536-543), float64 [ncols, M]."""
+    """a as the adjoint kernels read it: the fp32 sum of the two leading bf16 planes (`unpack` in the EPI_INBWD epilogue), float64 [ncols, M]."""
     n, rows, C = ap.shape
     f = ap[0].float() + ap[1].float()
     return unblock(f.view(1, rows, C))[0]
@@ -213,7 +213,7 @@ def fused_adjoint(WTp, dYnp, ap, rstd, gamma, beta, slope):
 
 
 def tn_slices(ncols, slices):
-    """(begin, end) columns of each slice of dfepe_est_gemm_tn (est_gemm.hip:1867-1868, 776-778); end <= begin: empty."""
+    """(begin, end) columns of each slice of dfepe_est_gemm_tn (its cps; kbeg, kend of est_gemm_tn_body); end <= begin: empty."""
     cps = ((ncols + slices - 1) // slices + 31) // 32 * 32
     return [(s * cps, min(s * cps + cps, ncols)) for s in range(slices)]
 

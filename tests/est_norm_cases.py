@@ -1,15 +1,15 @@
-"""The case matrix of the estimator's any-N normalisation, adjoint, head and reduction kernels (csrc/est_gemm.hip) and one check_*() per
+"""The case matrix of the estimator's any-N normalisation, adjoint, head and reduction kernels (csrc/est_norm.hip, est_colsum in csrc/est_planes.hip) and one check_*() per
 entry point, shared by the host test (tests/test_est_norm_ref_cpu.py: an fp32 evaluation in torch and mutations of it) and the device
 test (tests/test_est_norm_edges_gpu.py).  The reference and every bound are tests/est_norm_ref.py's; the buffers (PlaneBuf, row_buf,
 MARGIN), the undecided cap and affine() are tests/est_gemm_cases.py's.
 
-Launch geometry, restated once from est_gemm.hip:
-  register-resident pair (dfepe_est_norm_fwd_r / _in_bwd_r, lines 2104-2107, 2127-2130): template (RPT, CP) = (2, 16) N <= 128, (8, 16)
+Launch geometry, restated once from est_norm.hip:
+  register-resident pair (the N ladders of dfepe_est_norm_fwd_r / dfepe_est_in_bwd_r): template (RPT, CP) = (2, 16) N <= 128, (8, 16)
       N <= 512, (16, 16) N <= 1024, (16, 8) N <= 2048; 1024 / CP row groups, thread (cp, rg) owns rows rg, rg + RG, ...; a row sum is
-      RPT additions in the thread, log2(64 / CP) cross-lane, 15 through LDS (rg_all_sum, lines 1214-1233)
+      RPT additions in the thread, log2(64 / CP) cross-lane, 15 through LDS (rg_all_sum)
   strided pair (dfepe_est_norm_fwd / _in_bwd_n): 32 row groups x 4 rows in flight, splits = 1..64 workgroups per pair, split t owns rows
       [t R, min((t + 1) R, N)), R = ceil(N / splits); a split's sum is ceil(R / 32) additions in the thread and 32 through LDS
-      (pair_reduce2, lines 980-987); the adjoint adds the `splits` partial sums in order
+      (pair_reduce2); the adjoint adds the `splits` partial sums in order
   dfepe_est_in_bwd (N = 100): 8 row groups of 13 rows, 8 partials through LDS
 Every output and the `part` workspace carry margins and are NaN throughout before the call: check_*() asserts that the margins are
 still NaN and that everything inside is finite and within TOL * bound of the restatement.  Per-pair d gamma / d beta rows and per-block

@@ -1,6 +1,6 @@
-"""fp64 restatement of the estimator's any-N normalisation, adjoint, head and reduction kernels (csrc/est_gemm.hip: est_norm_fwd_r_kernel,
+"""fp64 restatement of the estimator's any-N normalisation, adjoint, head and reduction kernels (csrc/est_norm.hip: est_norm_fwd_r_kernel,
 est_norm_fwd_n_kernel<0|1|2>, est_in_bwd_r_kernel, est_in_bwd_n_kernel<0|1|2>, est_in_bwd_kernel, est_head_fwd_kernel, est_head_dw_kernel,
-est_colsum_kernel, est_dgamma_zero_kernel; csrc/inorm.hip: inorm_lrelu_*_kernel) that tests/est_norm_cases.py holds them to, element by
+est_dgamma_zero_kernel; csrc/est_planes.hip: est_colsum_kernel; csrc/inorm.hip: inorm_lrelu_*_kernel) that tests/est_norm_cases.py holds them to, element by
 element.  torch float64, no GPU needed.  U, SLACK, TOL, GAMMA_MIN, the plane helpers and compare() are tests/est_gemm_ref.py's.
 
 Like that module it works from the VALUES of what a kernel reads -- the fp32 partial products, the planes' bits, the fp32 partial
@@ -10,9 +10,9 @@ Bounds (u = 2^-24; first order, x SLACK; each on |an fp32 evaluation - the exact
 of terms t_i whose longest chain of dependent additions is n is known to  n u sum|t_i|  in ANY order of that depth; every function
 takes `chain`, the n of the kernel that is being held (tests/est_norm_cases.py counts it from the source), default: the row count.
 ------------------------------------------------------------------------------------------------------------------------------------
-norm_forward   est_norm_fwd_r_kernel (est_gemm.hip:1248-1296), est_norm_fwd_n_kernel (:1010-1086).  It is EPI_IN's chain with N in
+norm_forward   est_norm_fwd_r_kernel, est_norm_fwd_n_kernel<0>.  It is EPI_IN's chain with N in
                place of 100 and two changes, both written down here:
-                 y = sum of the S partials in slice order (:1254-1261), value the fp64 sum     dy    = (S - 1) u sum_s |Y_s|
+                 y = sum of the S partials in slice order (the _r kernel's first loop), the fp64 sum   dy    = (S - 1) u sum_s |Y_s|
                  mu = (sum y) * fl(1 / N)                                                       dmu   = mean(dy) + (n + 2) u mean|y|
                  d = y - mu                                   h = dy + u |d| is the part of d's error that differs from row to row,
                                                               dmu the part common to all rows:  dd    = h + dmu
@@ -21,7 +21,7 @@ norm_forward   est_norm_fwd_r_kernel (est_gemm.hip:1248-1296), est_norm_fwd_n_ke
                  mean of 40 that bound is too wide to tell a one-pass variance from a two-pass one.  N dmu^2 is kept although it is
                  second order: it is all there is for a constant channel.)
                                                          dq    = N dmu^2 + sum (2 (|d| + dmu) h + h^2) + (n + 2) u q
-               merged statistics, est_norm_fwd_n_kernel<1> + <2> (:1036-1058): split t (n_t > 0 rows, R = ceil(N / S) apiece) leaves
+               merged statistics, est_norm_fwd_n_kernel<1> + <2> (the MODE 1 store and the MODE 2 merge): split t (n_t > 0 rows, R = ceil(N / S) apiece) leaves
                its own two-pass m_t, Q_t (dm_t, dQ_t as above with n_t for N); then over the T non-empty splits
                  mu = (sum_t fma(n_t, m_t)) / N                 dmu   = (sum n_t dm_t + T u sum n_t |m_t|) / N + u |mu|
                  d_t = m_t - mu                                 e_t   = dm_t + u |d_t|   (not common to the splits; dmu is)
@@ -32,7 +32,7 @@ norm_forward   est_norm_fwd_r_kernel (est_gemm.hip:1248-1296), est_norm_fwd_n_ke
                  rstd = 1 / sqrt(v): drstd = rstd (dv / (2 v) + 2 u);  k = rstd gamma: dk = |gamma| drstd + u |k|;
                  z = fma(d, k, beta): dz = |k| dd + |d| dk + u |z|;  a = z > 0 ? z : z slope: da = dz, or slope dz + u |a|
                planes: two fp16 max(2^-22 |a|, 2^-25), two bf16 2^-16 |a|, none (inorm_lrelu) 0.  undecided: |z| <= dz, widened by |z|.
-adjoint_n      est_in_bwd_r_kernel (:1323-1403), est_in_bwd_n_kernel (:1134-1195), est_in_bwd_kernel (:911-965).  Not EPI_INBWD's
+adjoint_n      est_in_bwd_r_kernel, est_in_bwd_n_kernel (its `item` and the two loops over it), est_in_bwd_kernel.  Not EPI_INBWD's
                arithmetic: a = the fp32 sum of the two stored planes (exact: same bits on both sides),
                  d = sum of the S partials in slice order          dd    = (S - 1) u sum_s |dA_s|;  head form dl w: u |d|
                  z = a, or a fl(1 / slope)                          dzz   = 0, or 2 u |z|
@@ -44,13 +44,13 @@ adjoint_n      est_in_bwd_r_kernel (:1323-1403), est_in_bwd_n_kernel (:1134-1195
                  t = e - m1 - x^ m2 (contracted or not)             dt    = de + dm1 + dx |m2| + |x^| dm2 + u |x^ m2| + u |e - m1| + u |t|
                  dY = (rstd gamma) t                                |k| dt + 2 u |dY|, and 2^-16 |dY| for the two bf16 planes
                The split form (est_in_bwd_n_kernel<1> + <2>) adds the S partial sums in order: S more additions in n.
-head_forward   est_head_fwd_kernel (:1412-1423): C / 16 fused multiply-adds per lane, four cross-lane additions, the bias:
+head_forward   est_head_fwd_kernel: C / 16 fused multiply-adds per lane, four cross-lane additions, the bias:
                (C / 16 + 5) u (sum|w a| + |bias|), a = the fp32 sum of the two fp16 planes (the kernel's own first operation).
-head_dw        est_head_dw_kernel (:1433-1480): block b owns columns [b cpb, min((b + 1) cpb, ncols)), cpb = ceil(ncols / blocks);
+head_dw        est_head_dw_kernel: block b owns columns [b cpb, min((b + 1) cpb, ncols)), cpb = ceil(ncols / blocks);
                a thread adds every eighth column, eight partial sums through LDS: (ceil(cpb / 8) + 8) u sum|dl a|; bias_part
                (ceil(cpb / 8) + 3) u sum|dl|.  A block without columns: exactly 0, both.
-colsum         est_colsum_kernel (:1636-1662): rows <= 32: rows additions in order; rows > 32: ceil(rows / 16) + 15.
-dgamma_zero    est_dgamma_zero_kernel (:1938-1965): y = W[ch] . x over Ci fused multiply-adds: dy = Ci u sum|W||x|;
+colsum         est_colsum_kernel (its WIDE and TALL branches): rows <= 32: rows additions in order; rows > 32: ceil(rows / 16) + 15.
+dgamma_zero    est_dgamma_zero_kernel (the loop over pairs): y = W[ch] . x over Ci fused multiply-adds: dy = Ci u sum|W||x|;
                mean = (sum y) / N, n = ceil(N / 256) + 8: dmean = mean(dy) + (n + 1) u mean|y|;
                x^ = (y - mean) rstd: dx = rstd (dy + dmean + u |y - mean|) + u |x^|;
                d = dA (exact), dl w (u |d|), or dY_next[col] . W_next[:, ch] (C_next u sum|..|);  dz as e above;
@@ -71,7 +71,7 @@ def sum_parts(parts):
 
 
 def split_rows(N, S):
-    """(begin, end) rows of each of the S splits of est_norm_fwd_n_kernel / est_in_bwd_n_kernel (est_gemm.hip:1001-1002); end <= begin: empty."""
+    """(begin, end) rows of each of the S splits of est_norm_fwd_n_kernel / est_in_bwd_n_kernel (their R, r0, r1); end <= begin: empty."""
     R = -(-N // S)
     return [(t * R, min(t * R + R, N)) for t in range(S)]
 
@@ -237,7 +237,7 @@ def head_forward(ap, w, bias):
 
 
 def head_blocks(ncols, blocks):
-    """(begin, end) columns of each block of dfepe_est_head_dw (est_gemm.hip:2146, 1433-1435); end <= begin: the block owns none."""
+    """(begin, end) columns of each block of dfepe_est_head_dw (its cpb; c0, c1 of est_head_dw_kernel); end <= begin: the block owns none."""
     cpb = -(-ncols // blocks)
     return [(b * cpb, min(b * cpb + cpb, ncols)) for b in range(blocks)]
 

@@ -127,7 +127,7 @@ def _fill(buf, planes):
 
 
 def emu_layer_fwd(case, Wp, Xp, scale, gamma, beta, slope, mut=None):
-    """est_gemm.hip:661-716 in torch fp32: sums, the difference first, the biased variance, one fused multiply-add's worth of z."""
+    """est_gemm_nt_kernel's EPI_IN epilogue in torch fp32: sums, the difference first, the biased variance, one fused multiply-add's worth of z."""
     _, M, pairs, K, absmax, keep = case
     ncols = pairs * KPTS
     y = emu_product(Wp, Xp, 1, scale)
@@ -156,7 +156,7 @@ def emu_layer_fwd(case, Wp, Xp, scale, gamma, beta, slope, mut=None):
 
 
 def emu_dgrad(case, WTp, dYnp, ap, rstd, gamma, beta, mut=None):
-    """est_gemm.hip:494-657 in torch fp32."""
+    """est_gemm_nt_kernel's EPI_INBWD epilogue in torch fp32."""
     _, M, pairs, K, slope = case
     ncols = pairs * KPTS
     dA = emu_product(WTp, dYnp, 1)

@@ -1,4 +1,4 @@
-"""The estimator's any-N normalisation, adjoint, head and reduction entry points (csrc/est_gemm.hip) on the device, over the case matrix
+"""The estimator's any-N normalisation, adjoint, head and reduction entry points (csrc/est_norm.hip, est_planes.hip) on the device, over the case matrix
 of tests/est_norm_cases.py and through its check_*(): each element against the fp64 restatement of tests/est_norm_ref.py, within TOL
 times its own first-order bound; NaN pre-filled outputs and `part` workspaces with margins; per-pair and per-block partials row by row;
 a second call on the same inputs bit for bit; refused arguments leave the outputs untouched.  Each test prints

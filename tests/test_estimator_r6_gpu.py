@@ -1,4 +1,4 @@
-"""Round 6 pieces of the weight estimator (csrc/est_gemm.hip; deepFEPE/models/ErrorEstimators.py:47-64 at the reference's own shapes,
+"""Round 6 pieces of the weight estimator (csrc/est_*.hip; deepFEPE/models/ErrorEstimators.py:47-64 at the reference's own shapes,
 N = 1000-2000 points and 4-12 pairs per batch, deepFEPE/configs/kitti_corr_baseline.yaml:12-13): split-K plain products, the
 register-resident normalisation and its adjoint (which add the split-K partials), every layer's weight gradient in one launch, the
 input gradient stored by its GEMM's epilogue, parameters prepared once per model forward -- each against float64 or against the launch
