@@ -1376,8 +1376,8 @@ int dfepe_epi_loss_bwd(void *stream, int kind, const float *F, const float *X, c
  * Refusals, made on the host before any HIP call, in this order: B or N < 0, H < 1, S outside 8..16, N < S, loss_kind outside 0..2:
  * INVALID_ARG.  Then B == 0 returns OK: nothing is launched and nothing written.  A NULL X, Y, K, idx, E_sample, score, E_refit,
  * loss, quality, counts, best or workspace; X or Y not 8-byte aligned; a workspace that is not 16-byte aligned: INVALID_ARG.
- * B * H * N > 2^31 - 1: UNSUPPORTED.  Not built: the adjoint of the loop (the adjoint of its two fits exists: dfepe_eight_point_bwd
- * below), a device-side sampler, losses other than the two above.
+ * B * H * N > 2^31 - 1: UNSUPPORTED.  The adjoint of the loop is dfepe_dsac_bwd below.  Not built: a device-side sampler, losses other
+ * than the two above.
  */
 int dfepe_dsac_hyps_per_block(void);
 int dfepe_dsac_vote_chunk(void);
@@ -1439,6 +1439,68 @@ size_t dfepe_eight_point_bwd_workspace_bytes(int B, int N, int n_weight_sets);
 int dfepe_eight_point_bwd(void *stream, const float *X, const float *Y, const float *w, int B, int N, int n_weight_sets,
                           unsigned flags, const float *F_out, const float *g_F,
                           float *g_X, float *g_Y, float *g_w, void *workspace);
+
+/*
+ * Adjoint of the DSAC loop: the gradients of dfepe_dsac's E_sample, score, E_refit, loss, quality and exp_loss w.r.t. the pixel
+ * points X and Y (csrc/dsac_adjoint.hip, csrc/dsac_adjoint_math.h).  The conventions are dfepe_dsac's: fp32 in and out, fp64
+ * inside, every output rounded once; no atomics, no allocation, no host synchronisation; one linear chain of eight launches (seven with H = 1, where the refits' adjoint needs no set sum) whatever
+ * B and H are (capturable); a pair's bits do not depend on the run or on the rest of the batch; a non-finite input stays in its own
+ * pair.  dfepe_version() stays 154 with this addition: nothing that existed changes.
+ *
+ * The function differentiated is the forward as dfepe_dsac documents it, stages 1-5 on the fp32 values it wrote; each fp32 rounding
+ * between stages is taken as the identity.  K is a CONSTANT: its gradient is not built.  soft, sampson, counts, best and top_loss
+ * take no upstream.  The Hartley transforms of both fits are constants, as in dfepe_eight_point_bwd.
+ *
+ *   X, Y, K, idx, B, N, H, S, inlier_beta, inlier_alpha, loss_kind: as given to dfepe_dsac (inlier_thresh is not read: `soft` is)
+ *   E_sample [B,H,9], soft [B,H,N], score [B,H], E_refit [B,H,9], loss [B,H], counts [B,N]: the forward's outputs as written
+ *   g_E_sample [B,H,9], g_score [B,H], g_E_refit [B,H,9], g_loss [B,H], g_quality [B,N], g_exp_loss [B]: upstream gradients, each
+ *     may be NULL (= 0), not all of them
+ *   g_X, g_Y [B,N,2] (8-byte aligned): written, not accumulated; one of the two may be NULL
+ *   t_score, t_loss [B,H], t_E_refit [B,H,9], t_w [H,B,N], t_E_sample [B,H,9]: the stage totals below, each may be NULL (it then
+ *     lives in the workspace only)
+ *   workspace: dfepe_dsac_bwd_workspace_bytes(B, N, H, S) bytes, 16-byte aligned, contents irrelevant.  In floats, every section
+ *     rounded up to a multiple of 4: 2 x 2BN (K^-1 points), 2 x 2BHS (gathered samples), BHN (weights), 2 x 9BH (E_refit and t_E_refit
+ *     as [H,B,9]), BH, BH, 9BH, BHN, 9BH (the five totals), 2 x 2BN, 2 x 2BHS (the fits' point gradients), 2 x 18BH (F_h, M_h in fp64),
+ *     and dfepe_eight_point_bwd_workspace_bytes(B, N, H) / 4.
+ *
+ * Launches, with p = softmax(alpha score) and Lbar = sum_h p_h loss_h recomputed in fp64 from the fp32 score and loss,
+ * max-subtracted as the vote does:
+ *   1 prep     the K^-1 points and the gathered samples (ds::inv3, ds::normalized_point) in the 2-D layout dfepe_eight_point_bwd reads;
+ *              w = sqrt(soft) rounded to fp32 as the forward formed it, [H,B,N]; F_h = K^-T E_sample K^-1 and M_h (E_refit with
+ *              loss_kind 1, K^-T E_refit K^-1 with 2) in fp64.  The forward's workspace is not kept: all of it is recomputed.
+ *   2 head     t_loss = g_loss + g_exp_loss[b] p_h;  t_score = g_score + g_exp_loss[b] alpha p_h (loss_h - Lbar)
+ *              + sum_{j<S} g_quality[b, idx[b,h,j]] / (counts[b, idx[b,h,j]] + 1e-10), in slot order; an index outside 0..N-1
+ *              contributes nothing, as in the vote.
+ *   3 loss     t_M = (t_loss / N) sum_n d sampson(M_h; x_n, y_n) / dM, summed in the order of the forward's stage 4;
+ *              t_E_refit = g_E_refit + t_M (kind 1) or + K^-1 t_M K^-T (kind 2); = g_E_refit with loss_kind 0.
+ *   4-5 refit  dfepe_eight_point_bwd with H weight sets, w, F_out = E_refit, g_F = t_E_refit, SQRT2 | NO_ROWNORM | FORCE_110:
+ *              t_w [H,B,N] and the gradient to the K^-1 points summed over the sets.
+ *   6 score    c[b,h,n] = -beta (1 - s)(s t_score + w t_w / 2), s the fp32 soft as written.  No division: where s = 0 (the
+ *              reference's sqrt(1 - sigmoid) backpropagates inf * 0 = NaN there) c = 0, the limit of d sqrt(s)/dd =
+ *              -(beta/2) sqrt(s)(1 - s); a NaN stays a NaN.  t_F = sum_n c d sampson(F_h)/dF, t_E_sample = g_E_sample + K^-1 t_F K^-T.
+ *   7 sample   dfepe_eight_point_bwd on the B H gathered problems of S points, F_out = E_sample, g_F = t_E_sample.
+ *   8 points   one lane per correspondence: the refit's K^-1 gradient plus the sample fits' of every (h, j) with idx[b,h,j] == n,
+ *              through the Jacobian of _de_homo(K^-1 .) with its 1e-10 guard, plus the direct pixel terms
+ *              sum_h [c d d_h/dx + (t_loss_h / N) d l_h/dx].  A workgroup owns 64 correspondences; its wavefront v adds the
+ *              hypotheses [v Hq, (v+1) Hq), Hq = ceil(H/4), ascending, per hypothesis the slots ascending, then the score's term,
+ *              then the loss's; wavefront 0 adds the four partial sums in wavefront order, the refit's gradient first.
+ *
+ * Refusals, made on the host before any HIP call, in this order: B or N < 0, H < 1, S outside 8..16, N < S, loss_kind outside 0..2:
+ * INVALID_ARG.  Then B == 0 returns OK: nothing is launched and nothing written.  A NULL X, Y, K, idx, E_sample, soft, score,
+ * E_refit, loss, counts or workspace: INVALID_ARG.  Every upstream NULL: INVALID_ARG.  g_X and g_Y both NULL: INVALID_ARG.  X, Y,
+ * g_X or g_Y not 8-byte aligned, or a workspace that is not 16-byte aligned: INVALID_ARG.  B * H * N > 2^31 - 1: UNSUPPORTED.
+ * Not built: the gradient to K, upstreams for soft, sampson and top_loss.
+ */
+size_t dfepe_dsac_bwd_workspace_bytes(int B, int N, int H, int S);
+int dfepe_dsac_bwd(void *stream, const float *X, const float *Y, const float *K, const int *idx, int B, int N, int H, int S,
+                   float inlier_thresh, float inlier_beta, float inlier_alpha, int loss_kind,
+                   const float *E_sample, const float *soft, const float *score, const float *E_refit, const float *loss,
+                   const float *counts,
+                   const float *g_E_sample, const float *g_score, const float *g_E_refit, const float *g_loss, const float *g_quality,
+                   const float *g_exp_loss,
+                   float *g_X, float *g_Y,
+                   float *t_score, float *t_loss, float *t_E_refit, float *t_w, float *t_E_sample,
+                   void *workspace);
 
 #ifdef __cplusplus
 }

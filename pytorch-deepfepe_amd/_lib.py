@@ -174,6 +174,8 @@ _SIGNATURES = {
     "dfepe_dsac": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int] + [_P] * 12),
     "dfepe_eight_point_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_eight_point_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_uint, _P, _P, _P, _P, _P, _P]),
+    "dfepe_dsac_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dfepe_dsac_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int] + [_P] * 20),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -9,10 +9,11 @@ batch and all its hypotheses go through six launches, without a host synchronisa
 The reference calls an undefined `utils_F.E_to_F` at :67 (only `_E_to_F` exists); its evident intent, F = K^-T E K^-1, is
 what is computed.  Its prints are not mirrored.
 
-Not built: the adjoint of the loop (inputs that require grad raise NotImplementedError; the adjoint of its two fits exists,
-ops.eight_point / dfepe_eight_point_bwd, the loop's own is what is missing), a device-side sampler, and `loss_function`s
+The adjoint of the loop is dfepe_dsac_bwd: dsac_batch and DSAC.expected_loss are differentiable w.r.t. X and Y through ops.dsac.
+DSAC.__call__ is the reference's call and returns a CPU tensor without a graph: inputs that require grad raise NotImplementedError
+there; expected_loss is the differentiable entry.  Not built: the gradient to K, a device-side sampler, and `loss_function`s
 other than H_loss.HLoss on the fused path: any other callable is evaluated per hypothesis on the refitted E, one call and
-its launches per hypothesis -- the slow route.
+its launches per hypothesis -- the slow route, forward only.
 """
 import random
 
@@ -80,6 +81,37 @@ class DSAC:
             self.best_H, self.best_H_idx, self.best_dists = E_refit[best], best, self.inlier_scores[best]
             self.best_corres_idx = idx_list[best]
         return r["quality"][0].unsqueeze(1).cpu()
+
+    def expected_loss(self, X, Y):
+        """The training step the reference leaves commented out (dsac.py:178-190), differentiable: X, Y [N,2] pixel
+        correspondences -> (exp_loss, top_loss), device scalars; exp_loss = sum_h softmax(alpha score)_h loss_h carries the graph to
+        X and Y (ops.dsac, dfepe_dsac_bwd), top_loss = loss[best] does not.  Draws the seeded minimal sets __call__ draws and sets
+        the attributes __call__ sets (none of those carries a graph), plus ``quality`` [N,1] on the device with its graph.  Needs the
+        fused loss, H_loss.HLoss: any other callable raises NotImplementedError.  K is a constant of the adjoint."""
+        if not isinstance(self.loss_function, HLoss):
+            raise NotImplementedError("compat.dsac.DSAC.expected_loss: only H_loss.HLoss is fused into the loop and its adjoint; "
+                                      "the adjoint of an arbitrary loss_function is not built")
+        X, Y = torch.as_tensor(X), torch.as_tensor(Y)
+        N, H = X.shape[0], self.hyps
+        assert Y.shape[0] == N, "N mismatch between X and Y!"
+        self.N = N
+        idx_list = _draw(N, H, SAMPLE)
+        dev = _device_of(X, Y)
+        X, Y = X.to(dev, torch.float32), Y.to(dev, torch.float32)
+        K = torch.as_tensor(self.K, dtype=torch.float32).to(dev)
+        idx = torch.tensor(idx_list, dtype=torch.int32).to(dev)
+        r = ops.dsac(X[None], Y[None], K.reshape(1, 3, 3), idx[None], self.inlier_thresh, self.inlier_beta, self.inlier_alpha, loss_kind=1)
+        self.inlier_scores, self.sampson_dists = r["soft"][0], r["sampson"][0]
+        self.hyp_scores, E_refit = r["score"][0].detach(), r["E_refit"][0].detach()
+        self.hyp_losses, self.exp_loss, self.top_loss = r["loss"][0].detach(), r["exp_loss"][0], r["top_loss"][0]
+        self.quality = r["quality"][0].unsqueeze(1)
+        best = int(r["best"][0].item())  # the one host synchronisation of the call
+        self.max_score = 0
+        if best >= 0:
+            self.max_score = float(self.hyp_scores[best].item())
+            self.best_H, self.best_H_idx, self.best_dists = E_refit[best], best, self.inlier_scores[best]
+            self.best_corres_idx = idx_list[best]
+        return self.exp_loss, self.top_loss
 
 
 def dsac_batch(X, Y, K, hyps, inlier_thresh, inlier_beta, inlier_alpha=0.0, idx=None, seed=None, sample=SAMPLE, loss_kind=0,
