@@ -19,7 +19,7 @@ import random
 
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from .H_loss import HLoss
 
 SAMPLE = 10  # correspondences per hypothesis (dsac.py:46)
@@ -121,7 +121,7 @@ def dsac_batch(X, Y, K, hyps, inlier_thresh, inlier_beta, inlier_alpha=0.0, idx=
     as given; otherwise it is drawn on the host -- random.Random(seed), pair by pair, hypothesis by hypothesis, random.sample as
     the reference draws -- and copied once.  No host synchronisation after that."""
     if not (torch.is_tensor(X) and X.is_cuda):
-        raise ops._lib.DfepeError("compat.dsac.dsac_batch: X, Y must live on the GPU (this package has no CPU path)")
+        raise _lib.DfepeError("compat.dsac.dsac_batch: X, Y must live on the GPU (this package has no CPU path)")
     B, N = X.shape[0], X.shape[1]
     K = torch.as_tensor(K, dtype=torch.float32).to(X.device)
     if K.dim() == 2:

@@ -30,10 +30,7 @@ FAILED = (180.0, 90.0)    # the pose-error values of a pair without a pose (util
 def recover_pose_camera(K):
     """K [B,3,3] (device) -> the camera the reference hands cv2.recoverPose: focal K[0,0], principal point (K[0,2], K[1,2])
     (utils_opencv.py:177)."""
-    Kp = torch.zeros_like(K)
-    Kp[:, 0, 0] = Kp[:, 1, 1] = K[:, 0, 0]
-    Kp[:, 0, 2], Kp[:, 1, 2], Kp[:, 2, 2] = K[:, 0, 2], K[:, 1, 2], 1.0
-    return Kp
+    return ops._recover_pose_camera(K)
 
 
 def triangulatePoints(projMatr1, projMatr2, projPoints1, projPoints2):

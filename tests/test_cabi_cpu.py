@@ -29,6 +29,58 @@ def test_library_builds_and_exports_every_declared_symbol(dfepe):
     assert sorted(dfepe.EXPORTED_SYMBOLS) == declared  # the ctypes table covers exactly the header
 
 
+_C_SCALARS = {"int": ctypes.c_int, "unsigned": ctypes.c_uint, "unsigned int": ctypes.c_uint, "float": ctypes.c_float,
+              "double": ctypes.c_double, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "unsigned long long": ctypes.c_ulonglong,
+              "uint64_t": ctypes.c_ulonglong}
+
+
+def _ctype_of(decl, what, is_return=False):
+    """The ctypes counterpart of one C declarator (a parameter with or without its name, or a return type).  A type this does
+    not know raises: the test then fails, it does not pass over the prototype."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl:
+        return ctypes.c_char_p if is_return and decl.replace("const ", "") == "char *" else ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    for ctype in (" ".join(words), " ".join(words[:-1])):  # unnamed, or the last word is the parameter's name
+        if ctype in _C_SCALARS:
+            return _C_SCALARS[ctype]
+    raise AssertionError(f"{what}: no ctypes counterpart known for the C type in {decl!r}")
+
+
+def _declared_prototypes():
+    """name -> (restype, [argtypes]) of every prototype of include/dfepe.h."""
+    text = open(os.path.join(REPO, "include", "dfepe.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|^\s*\}', " ", text, flags=re.M)
+    protos = {}
+    for stmt in text.split(";"):
+        if not stmt.strip():
+            continue
+        m = re.fullmatch(r"\s*([\w\s\*]+?)\s*\b(dfepe_[a-z0-9_]+)\s*\(([^()]*)\)\s*", stmt)
+        assert m, f"include/dfepe.h: not a prototype the test can read: {stmt.strip()[:80]!r}"
+        ret, name, args = m.groups()
+        args = [] if args.strip() in ("", "void") else [_ctype_of(a, name) for a in args.split(",")]
+        assert name not in protos, f"{name} declared twice"
+        protos[name] = (_ctype_of(ret, name, is_return=True), args)
+    return protos
+
+
+def test_ctypes_table_matches_the_header_by_type(dfepe):
+    """dfepe._lib._SIGNATURES against include/dfepe.h: the return type and every argument type of every entry point (an int
+    bound where the header says size_t would corrupt the arguments behind it without any error)."""
+    protos = _declared_prototypes()
+    table = dfepe._lib._SIGNATURES
+    assert sorted(protos) == sorted(table) == _declared_symbols()
+    for name, (res, args) in protos.items():
+        t_res, t_args = table[name]
+        assert t_res is res, f"{name}: returns {res.__name__} in the header, {t_res.__name__} in the ctypes table"
+        assert len(t_args) == len(args), f"{name}: {len(args)} arguments in the header, {len(t_args)} in the ctypes table"
+        for i, (a, b) in enumerate(zip(args, t_args)):
+            assert a is b, f"{name}: argument {i} is {a.__name__} in the header, {b.__name__} in the ctypes table"
+
+
 def test_version_strerror_and_save_layout(dfepe):
     L = dfepe._lib.lib()
     assert L.dfepe_version() == 154
