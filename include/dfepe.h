@@ -1376,8 +1376,8 @@ int dfepe_epi_loss_bwd(void *stream, int kind, const float *F, const float *X, c
  * Refusals, made on the host before any HIP call, in this order: B or N < 0, H < 1, S outside 8..16, N < S, loss_kind outside 0..2:
  * INVALID_ARG.  Then B == 0 returns OK: nothing is launched and nothing written.  A NULL X, Y, K, idx, E_sample, score, E_refit,
  * loss, quality, counts, best or workspace; X or Y not 8-byte aligned; a workspace that is not 16-byte aligned: INVALID_ARG.
- * B * H * N > 2^31 - 1: UNSUPPORTED.  The adjoint of the loop is dfepe_dsac_bwd below.  Not built: a device-side sampler, losses other
- * than the two above.
+ * B * H * N > 2^31 - 1: UNSUPPORTED.  The adjoint of the loop is dfepe_dsac_bwd below, the device-side sampler that fills idx on the
+ * stream is dfepe_sample_sets at the end of this header.  Not built: losses other than the two above.
  */
 int dfepe_dsac_hyps_per_block(void);
 int dfepe_dsac_vote_chunk(void);
@@ -1501,6 +1501,52 @@ int dfepe_dsac_bwd(void *stream, const float *X, const float *Y, const float *K,
                    float *g_X, float *g_Y,
                    float *t_score, float *t_loss, float *t_E_refit, float *t_w, float *t_E_sample,
                    void *workspace);
+
+/*
+ * The device-side sampler of the DSAC loop: idx [B,H,S] of dfepe_dsac drawn on the stream (csrc/sampler.hip, csrc/sampler_math.h),
+ * uniformly (the law of random.sample(range(n), S) for the SET, dsac.py:46) or in proportion to per-correspondence weights without
+ * replacement (np.random.choice(n, topK, p=p) of DeepFNetSampleLoss.Fit.forward).  Integer arithmetic only: the kernel, the host
+ * build of sampler_math.h and the restatement tests/sampler_ref.py agree bit for bit.  No atomics, no allocation, no host
+ * synchronisation, one linear chain of launches (two when weighted, else one): capturable, and with `counter` advanced by
+ * dfepe_sampler_advance inside the capture every replay of the graph draws fresh sets.  dfepe_version() stays 154 with this addition:
+ * nothing that existed changes.
+ *
+ *   seed, offset, counter   Philox4x32-10 with key = (seed & 0xffffffff, seed >> 32) and counter = (k, h, b, off): block k of
+ *        hypothesis h of pair b, off = offset + (counter ? *counter : 0) mod 2^32, `counter` one unsigned on the device, read by the
+ *        kernel.  Block k gives the words 4k .. 4k+3; draw j of a hypothesis uses r64 = word[2j+1] << 32 | word[2j]: exactly 2 S words,
+ *        no rejection loop.  A set depends on (seed, off, b, h, n, S) and its pair's weights only: not on B, H, the launch or the run.
+ *   bounded integer   t = mulhi64(r64, range), bias at most range / 2^64 per draw (< 2^-33 uniform; weighted: range < N 2^30).
+ *   n_valid [B] int32 or NULL (= N): only the first n = clamp(n_valid[b], S, N) correspondences of pair b can be drawn (the
+ *        reference's matches_good_unique_nums).
+ *   weights NULL: uniform mode, Floyd's subset algorithm: for i = 0 .. S-1, j = n - S + i, t = mulhi64(r64_i, j + 1), take j if t is
+ *        already in the set, else t; indices in the order generated (the order within a set is not uniform and need not be: the fit and
+ *        the vote are symmetric in the sample).  No memory is read but n_valid and counter; N up to 2^31 - 1.
+ *   weights [B,N]: weighted mode.  Per pair: a weight that is NaN, +-inf or <= 0 has q = 0; m = the largest other weight among the
+ *        first n, m = f 2^e with f in [0.5, 1); q_i = floor(w_i 2^(30 - e)) by shifting the significand (exact, no division), so
+ *        max q lies in [2^29, 2^30) and weights below 2^-30 m have q = 0 and are never drawn.  Launch 1, one workgroup per pair,
+ *        writes the exclusive prefix sums P[0 .. n] (uint64) in chunks of dfepe_sampler_scan_chunk() weights with a carry.  Draw k:
+ *        total = P[n] - sum of the chosen q, t = mulhi64(r64_k, total); walk the chosen indices c in ascending order with rem = 0,
+ *        while t + rem >= P[c] add q[c] to rem, stop at the first c where that fails; the index drawn is the largest i < n with
+ *        P[i] <= t + rem (binary search): never a chosen one, never one with q = 0.
+ *        A pair with fewer than S indices of q > 0 is drawn in uniform mode, and fallback[b] = 1.
+ *   idx [B,H,S] int32: written; distinct within a hypothesis and in [0, n): dfepe_dsac's contract.
+ *   fallback [B] int32 or NULL: 1 where a weighted pair was drawn uniformly, else 0 (always 0 in uniform mode).
+ *   workspace: dfepe_sample_sets_workspace_bytes(B, N, weighted) bytes, 16-byte aligned, contents irrelevant: B (N + 2) uint64 (P and
+ *        the number of q > 0 of every pair), rounded up to 16 bytes; 0 bytes (NULL allowed) when not weighted.
+ * Launch 2: one lane per hypothesis, a grid tail draws nothing; each wavefront writes its sets as consecutive words.
+ *
+ * Refusals, made on the host before any HIP call, in this order: B or N < 0, H < 1, S outside 8..16, N < S: INVALID_ARG.  Then
+ * B == 0 returns OK: nothing is launched and nothing written.  A NULL idx: INVALID_ARG.  Weighted with a NULL workspace or one that is
+ * not 16-byte aligned: INVALID_ARG.  B * H * S > 2^31 - 1: UNSUPPORTED.  Weighted with N > 2^20: UNSUPPORTED.
+ *
+ * dfepe_sampler_advance: a one-thread launch, *counter += by (mod 2^32).  A NULL counter: INVALID_ARG.
+ * Not built: a sampler that replays random.sample's Mersenne Twister stream.
+ */
+int dfepe_sampler_scan_chunk(void);
+size_t dfepe_sample_sets_workspace_bytes(int B, int N, int weighted);
+int dfepe_sample_sets(void *stream, int B, int N, int H, int S, unsigned long long seed, unsigned offset, const unsigned *counter,
+                      const float *weights, const int *n_valid, int *idx, int *fallback, void *workspace);
+int dfepe_sampler_advance(void *stream, unsigned *counter, unsigned by);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ SP_MAX_PIXELS = 1 << 24  # dfepe_sp_*: pixels per image (sp::kMaxPixels, csrc/sp
 SP_LDS_PIXELS = 12288  # dfepe_sp_nms: pixels per image up to which no workspace is needed (sp::kLdsPixels)
 SP_MAX_PATCH = 63  # dfepe_sp_soft_argmax: largest patch_size (sp::kMaxPatch)
 DSAC_MIN_SAMPLE, DSAC_MAX_SAMPLE = 8, 16  # dfepe_dsac: correspondences per hypothesis (ds::kMinSample, ds::kMaxSample)
+SAMPLER_MAX_WEIGHTED_N = 1 << 20  # dfepe_sample_sets: correspondences per pair in weighted mode (sm::kMaxWeightedN)
 INLIER_TABLE_MAX_THDS = 16  # dfepe_inlier_table: inlier thresholds per call, and mask thresholds per call (ce::kMaxThds)
 
 _P = c_void_p
@@ -176,6 +177,10 @@ _SIGNATURES = {
     "dfepe_eight_point_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_uint, _P, _P, _P, _P, _P, _P]),
     "dfepe_dsac_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dfepe_dsac_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int] + [_P] * 20),
+    "dfepe_sampler_scan_chunk": (c_int, []),
+    "dfepe_sample_sets_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dfepe_sample_sets": (c_int, [_P, c_int, c_int, c_int, c_int, c_ulonglong, c_uint, _P, _P, _P, _P, _P, _P]),
+    "dfepe_sampler_advance": (c_int, [_P, _P, c_uint]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -20,7 +20,8 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
     deepFEPE.evaluate_frontend          ->   compat.evaluate_frontend (matching score, nn mean AP, the five numbers per pair)
     deepFEPE.dsac_tools.utils_vis       ->   compat.utils_vis       (reproj_and_scatter without the drawing)
     deepFEPE.dsac_tools.dsac            ->   compat.dsac            (DSAC: the hypothesis loop in six launches; dsac_batch: a whole batch
-                                                                    of pairs on the device)
+                                                                    of pairs on the device; DeviceSampler: the minimal sets drawn on
+                                                                    the stream, uniform or by weight)
     superpoint.models.model_wrap        ->   compat.model_wrap      (PointTracker: nn_match_two_way and the two-frame state)
     superpoint.models.model_utils,      ->   compat.superpoint_process (flattenDetection, SuperPointNet_process: what
     superpoint.utils.utils                                          process_SP_output calls; the network stays the caller's)
@@ -39,7 +40,7 @@ from . import DeepFNet, ErrorEstimators, H_loss, captured, descriptor_evaluation
 from .captured import CapturedStep  # noqa: F401
 from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
 from .detector_evaluation import compute_repeatability, compute_repeatability_batch  # noqa: F401
-from .dsac import DSAC, dsac_batch  # noqa: F401
+from .dsac import DSAC, DeviceSampler, dsac_batch  # noqa: F401
 from .evaluate_frontend import frontend_metrics_batch  # noqa: F401
 from .evaluation_epiDist import correspondence_eval_batch  # noqa: F401
 from .utils_opencv import findHomography, findHomography_batch  # noqa: F401
