@@ -95,6 +95,27 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 
+// Position of each lane's kept item in the compact, order-preserving list of a workgroup of WAVES wavefronts (ballot prefix per
+// wave, wave totals in wsum[WAVES] in LDS); every lane of the workgroup calls it.  base: items before this trip, advanced by the
+// trip's total.
+template <int WAVES>
+__device__ inline int compact_slot(bool keep, int* wsum, int& base) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long bal = __ballot(keep);
+  const int before = __popcll(bal & ((1ull << lane) - 1ull)), total = __popcll(bal);
+  __syncthreads();  // wsum of the trip before has been read
+  if (lane == 0) wsum[wave] = total;
+  __syncthreads();
+  int off = base, all = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) {
+    if (w < wave) off += wsum[w];
+    all += wsum[w];
+  }
+  base += all;
+  return off + before;
+}
+
 template <bool RAW>
 __device__ __forceinline__ Pt global_point(const float* __restrict__ pts1, const float* __restrict__ pts2, size_t pair,
                                            int i, int N, float hw_sx, float hw_sy) {

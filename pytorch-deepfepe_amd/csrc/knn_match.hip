@@ -7,12 +7,12 @@
 // OpenCV's k-best insertion visits the columns in increasing order with a strict <, so the two neighbours of a query are
 // its two smallest (distance, column) pairs; the ratio line is Python: float64(m.distance) < ratio * float64(n.distance).
 //
-// Kernel 1 (knn_match_tile): the fp32 MFMA distance tile of match.hip (its LDS-staged main loop is copied, not shared:
-// match.hip stays as it is) -- one 256-thread workgroup per 128x128 tile, 2x2 wavefronts of 64x64, K = D in chunks of 16
-// staged K-major in LDS, double-buffered, XCD-aware tile order.  New here:
-//   * squared norms: every loader thread streams one whole descriptor row, so it also accumulates that row's sum of
-//     squares, one fmaf per component in increasing k, and leaves it in LDS (1 KiB) for the epilogue.  Bitwise-equal rows
-//     therefore have bitwise-equal norms in every tile;
+// Kernel 1 (knn_match_tile): the fp32 MFMA tile of match.hip, shared with it as mfma_dot_tile of match_tile.h -- one
+// 256-thread workgroup per 128x128 tile, 2x2 wavefronts of 64x64, K = D in chunks of 16 staged K-major in LDS,
+// double-buffered, XCD-aware tile order.  Its own:
+//   * squared norms: every loader thread streams one whole descriptor row, so the callable it hands to the tile accumulates
+//     that row's sum of squares, one fmaf per component in increasing k, and the kernel leaves it in LDS (1 KiB) for the
+//     epilogue.  Bitwise-equal rows therefore have bitwise-equal norms in every tile;
 //   * epilogue: t = fma(-2, dot, n1 + n2), a non-positive t becomes +0.0f (not fmaxf: it may return -0.0f, whose bits
 //     would sort last as an unsigned key); columns >= N2 carry the kNoVal key;
 //   * per row the TWO smallest (t bits << 32 | column) keys: in-lane over the two column tiles, then the transposing
@@ -25,18 +25,11 @@
 // Kernel 2 (knn_match_finish): one block per pair: merge the row's slots, dist = sqrtf(t), the ratio decision in double,
 // order-preserving compaction (ballot / popcount) in passes of 1024 rows.  The compacted list has the layout of
 // dfepe_nn_match_two_way, so dfepe_gather_matches takes it unchanged.
-#include "dfepe_common.h"
+#include "match_tile.h"
 
 #include <math.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
-constexpr int TM = 128;  // tile edge (rows of image 1 x rows of image 2)
-constexpr int TK = 16;   // K chunk: 2 x 2 x 16 x 128 floats = 32 KiB of LDS per workgroup (+ 1 KiB of norms): four workgroups share a CU
-constexpr unsigned kNoVal = 0xffffffffu;
 
 // Squared L2 distance from the dot product and the sum of the two squared norms; <= 0 (and -0.0f) -> +0.0f.
 __device__ __forceinline__ float dot_to_t(float dot, float nsum) {
@@ -44,19 +37,6 @@ __device__ __forceinline__ float dot_to_t(float dot, float nsum) {
   return (t > 0.0f) ? t : 0.0f;
 }
 
-template <int CTRL>
-__device__ __forceinline__ u64 exchange_u64(u64 v) {
-  union { u64 k; int i[2]; } a, r;
-  a.k = v;
-  if (CTRL == 0) {  // lane ^ 16: crosses the 16-lane DPP rows
-    r.i[0] = __shfl_xor(a.i[0], 16, 64);
-    r.i[1] = __shfl_xor(a.i[1], 16, 64);
-  } else {
-    r.i[0] = __builtin_amdgcn_update_dpp(a.i[0], a.i[0], (CTRL == 0) ? 0xB1 : CTRL, 0xf, 0xf, false);
-    r.i[1] = __builtin_amdgcn_update_dpp(a.i[1], a.i[1], (CTRL == 0) ? 0xB1 : CTRL, 0xf, 0xf, false);
-  }
-  return r.k;
-}
 // The two smallest of {a1 <= a2} and {b1 <= b2}, all four distinct (every key carries its own column).
 __device__ __forceinline__ void merge2(u64& a1, u64& a2, u64 b1, u64 b2) {
   const u64 lo = (b1 < a1) ? b1 : a1, hi = (b1 < a1) ? a1 : b1;
@@ -85,75 +65,19 @@ knn_match_tile_kernel(const float* __restrict__ desc1, const float* __restrict__
                       u64* __restrict__ ws) {
   __shared__ float lds[2][2][TK][TM];  // [buffer][image][k][row]: 32 KiB
   __shared__ __attribute__((aligned(16))) float nrm[2][TM];  // [image][row]: squared norms of the tile's descriptors
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  // XCD-aware tile order (match.hip): every XCD is given whole pairs, so that its L2 holds ~2 pairs' descriptors
-  const int tn = (N2 + TM - 1) / TM, tm = (N1 + TM - 1) / TM;
-  const unsigned total = gridDim.x;
-  unsigned w = blockIdx.x;
-  if ((total & 7u) == 0u) w = (w & 7u) * (total >> 3) + (w >> 3);
-  const int b = (int)(w / (unsigned)(tm * tn));
-  const int trem = (int)(w % (unsigned)(tm * tn));
-  const int m0 = (trem / tn) * TM, n0 = (trem % tn) * TM;
-
-  // loader role: threads 0..127 stream one descriptor of image 1 each (64 contiguous bytes per chunk), 128..255 image 2
-  const int img = tid >> 7, lr = tid & 127;
-  const int grow = (img ? n0 : m0) + lr;
-  const bool rvalid = grow < (img ? N2 : N1);
-  const float* src = (img ? desc2 + (size_t)b * N2 * D : desc1 + (size_t)b * N1 * D) + (size_t)(rvalid ? grow : 0) * D;
-  float4 pre[TK / 4];
-  float nsq = 0.0f;  // sum of squares of my row, one fmaf per component in increasing k
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < TK / 4; ++q)
-      pre[q] = rvalid ? reinterpret_cast<const float4*>(src + k0)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto lstore = [&](int buf) {
-    float* dst = &lds[buf][img][0][lr];
+  f32x16 acc[2][2];
+  float nsq = 0.0f;  // sum of squares of my loader row, one fmaf per component in increasing k
+  const auto [b, m0, n0, wr, wc, h, jl] = mfma_dot_tile(desc1, desc2, N1, N2, D, lds, acc, [&nsq](const float4(&pre)[TK / 4]) {
 #pragma unroll
     for (int q = 0; q < TK / 4; ++q) {
-      dst[(4 * q + 0) * TM] = pre[q].x;
-      dst[(4 * q + 1) * TM] = pre[q].y;
-      dst[(4 * q + 2) * TM] = pre[q].z;
-      dst[(4 * q + 3) * TM] = pre[q].w;
       nsq = fmaf(pre[q].x, pre[q].x, nsq);
       nsq = fmaf(pre[q].y, pre[q].y, nsq);
       nsq = fmaf(pre[q].z, pre[q].z, nsq);
       nsq = fmaf(pre[q].w, pre[q].w, nsq);
     }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-  const int h = lane >> 5, jl = lane & 31;
-  gload(0);
-  lstore(0);
-  __syncthreads();
-  const int nk = D / TK;
-  for (int c = 0; c < nk; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nk) gload((c + 1) * TK);
-    const float* Ab = &lds[buf][0][h][wr * 64 + jl];
-    const float* Bb = &lds[buf][1][h][wc * 64 + jl];
-#pragma unroll
-    for (int kk = 0; kk < TK / 2; ++kk) {
-      const float a0 = Ab[2 * kk * TM], a1 = Ab[2 * kk * TM + 32];
-      const float b0 = Bb[2 * kk * TM], b1 = Bb[2 * kk * TM + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (c + 1 < nk) lstore(buf ^ 1);
-    __syncthreads();
-  }
-  nrm[img][lr] = nsq;  // rows beyond N1 / N2 loaded zeros: norm 0
+  });
+  const int tid = threadIdx.x, lane = tid & 63;
+  nrm[tid >> 7][tid & 127] = nsq;  // the loader's image and row; rows beyond N1 / N2 loaded zeros: norm 0
   __syncthreads();
 
   // ---- epilogue: C/D layout of the 32x32 tile: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----------
@@ -209,7 +133,7 @@ knn_match_finish_kernel(const u64* __restrict__ ws, int N1, int slots, double ra
                         int* __restrict__ nn2, float* __restrict__ dist1, float* __restrict__ dist2, int* __restrict__ m_idx1,
                         int* __restrict__ m_idx2, float* __restrict__ score, int* __restrict__ count) {
   __shared__ int wsum[16];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   int base = 0;
   for (int i0 = 0; i0 < N1; i0 += 1024) {
     const int i = i0 + tid;
@@ -231,24 +155,12 @@ knn_match_finish_kernel(const u64* __restrict__ ws, int N1, int slots, double ra
       // m.distance < ratio * n.distance as Python evaluates it: both distances widened to double, the product in double
       keep = !ratio_test || ((double)d < ratio * (double)d2);
     }
-    const u64 bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull)), total = __popcll(bal);
-    if (lane == 0) wsum[wave] = total;
-    __syncthreads();
-    int off = base, all = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      if (w < wave) off += wsum[w];
-      all += wsum[w];
-    }
+    const size_t p = (size_t)b * N1 + compact_slot<16>(keep, wsum, base);
     if (keep) {
-      const size_t p = (size_t)b * N1 + off + before;
       m_idx1[p] = i;
       m_idx2[p] = (int)j;
       score[p] = d;
     }
-    base += all;
-    __syncthreads();
   }
   if (tid == 0) count[b] = base;
 }
@@ -276,14 +188,11 @@ extern "C" int dfepe_knn_match(const float* desc1, const float* desc2, int B, in
   if (N2 < 2) return DFEPE_ERR_INVALID_ARG;  // no second neighbour: the reference's `for m, n in matches` raises ValueError
   if (!desc1 || !desc2 || !workspace || !nn1 || !nn2 || !dist1 || !dist2 || !m_idx1 || !m_idx2 || !score)
     return DFEPE_ERR_INVALID_ARG;
-  if (D % 32 != 0) return DFEPE_ERR_UNSUPPORTED;  // K is consumed in 16-float chunks, two per 128-byte line (SIFT: D = 128)
-  if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15u) return DFEPE_ERR_INVALID_ARG;
-  if (((uintptr_t)workspace) & 7u) return DFEPE_ERR_INVALID_ARG;
-  const size_t tiles = (size_t)((N2 + TM - 1) / TM) * ((N1 + TM - 1) / TM) * B;
-  if (tiles > 0x7fffffffu) return DFEPE_ERR_UNSUPPORTED;
+  unsigned tiles;
+  if (const int rc = match_tile_plan(desc1, desc2, workspace, B, N1, N2, D, &tiles)) return rc;
   const int slots = (int)knn_slots(N2);
   u64* ws = static_cast<u64*>(workspace);
-  hipLaunchKernelGGL(knn_match_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, st, desc1, desc2, N1, N2, D, slots, ws);
+  hipLaunchKernelGGL(knn_match_tile_kernel, dim3(tiles), dim3(256), 0, st, desc1, desc2, N1, N2, D, slots, ws);
   hipLaunchKernelGGL(knn_match_finish_kernel, dim3(B), dim3(1024), 0, st, ws, N1, slots, ratio, ratio_test, nn1, nn2, dist1, dist2,
                      m_idx1, m_idx2, score, count);
   return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;

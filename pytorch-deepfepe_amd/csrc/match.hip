@@ -12,24 +12,15 @@
 //
 // Kernel 1 (nn_match_tile): the only GEMM-shaped op of the whole path, so it runs on the matrix cores in exact fp32
 // (v_mfma_f32_32x32x2_f32: the descriptors are fp32 and the arg-min decisions must not see bf16 rounding).  One
-// 256-thread workgroup per 128x128 tile of dmat, 2x2 wavefronts of 64x64 (2x2 MFMA tiles of 32x32, 64 accumulator
-// VGPRs), K = D in chunks of 16 staged K-major in LDS ([k][row]: a lane's MFMA operand A[i=l&31][k=l>>5] is then a
-// conflict-free ds_read_b32), double-buffered with the next chunk prefetched into registers.  dmat never reaches HBM:
+// 256-thread workgroup per 128x128 tile of dmat; the tile itself (placement, LDS staging, the double-buffered MFMA
+// loop) is mfma_dot_tile of match_tile.h, which knn_match.hip runs too.  dmat never reaches HBM:
 // the epilogue turns the accumulators into squared distances and folds them into per-row and per-column minima, packed
 // as (value bits << 32 | index) so that one 64-bit atomicMin per row/column realises numpy's first-occurrence argmin.
 // Kernel 2 (nn_match_finish): threshold + mutual check + order-preserving compaction (ballot / popcount).
 // Kernel 3 (gather_matches): the crop/pad gather into xs [B,N,4], offsets [B,N,4], quality [B,N].
-#include "dfepe_common.h"
+#include "match_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
-constexpr int TM = 128;  // tile edge (rows of image 1 x rows of image 2)
-constexpr int TK = 16;   // K chunk: 2 x 2 x 16 x 128 floats = 32 KiB of LDS per workgroup, so four workgroups share a CU and one
-                         // workgroup's epilogue / prologue overlaps the others' MFMA phases
-constexpr unsigned kNoVal = 0xffffffffu;
 
 // Squared distance of two unit descriptors from their dot product: t = 2 - 2 clip(dot, -1, 1), bit-identical to the
 // reference's fp32 expression under the square root (one rounding).  The minima are taken over t; the reference takes
@@ -38,19 +29,6 @@ constexpr unsigned kNoVal = 0xffffffffu;
 // ties (duplicated descriptors, dots clipped at 1) keep numpy's first-occurrence rule.  The score is sqrtf(t_min).
 __device__ __forceinline__ float dot_to_t(float dot) { return fmaf(-2.0f, __builtin_amdgcn_fmed3f(dot, -1.0f, 1.0f), 2.0f); }
 
-template <int CTRL>
-__device__ __forceinline__ u64 exchange_u64(u64 v) {
-  union { u64 k; int i[2]; } a, r;
-  a.k = v;
-  if (CTRL == 0) {  // lane ^ 16: crosses the 16-lane DPP rows
-    r.i[0] = __shfl_xor(a.i[0], 16, 64);
-    r.i[1] = __shfl_xor(a.i[1], 16, 64);
-  } else {
-    r.i[0] = __builtin_amdgcn_update_dpp(a.i[0], a.i[0], (CTRL == 0) ? 0xB1 : CTRL, 0xf, 0xf, false);
-    r.i[1] = __builtin_amdgcn_update_dpp(a.i[1], a.i[1], (CTRL == 0) ? 0xB1 : CTRL, 0xf, 0xf, false);
-  }
-  return r.k;
-}
 // One step of a transposing min-reduction over the 32 lanes of a half: CNT keys per lane -> CNT/2; the lane with the
 // decision bit set keeps the upper half of its array and hands the lower half to its partner (any partner on the other
 // side of the bit works: lane^16, row_mirror, row_half_mirror, quad_perm xor 2 / xor 1).  After the five steps lane j
@@ -71,71 +49,9 @@ __global__ void __launch_bounds__(256, 4)
 nn_match_tile_kernel(const float* __restrict__ desc1, const float* __restrict__ desc2, int N1, int N2, int D,
                      u64* __restrict__ rowkey, u64* __restrict__ colkey) {
   __shared__ float lds[2][2][TK][TM];  // [buffer][image][k][row]: 32 KiB
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  // XCD-aware tile order: workgroup w runs on XCD w % 8 (round-robin dispatch), and each XCD has its own 4 MiB L2.  The
-  // tiles of one image pair share its 2 x N x D descriptors, so every XCD is given whole pairs: the workgroups an XCD
-  // has in flight (32 CUs x 4) then cover ~2 pairs = ~4 MiB of descriptors instead of a slice of 16 different pairs.
-  const int tn = (N2 + TM - 1) / TM, tm = (N1 + TM - 1) / TM;
-  const unsigned total = gridDim.x;
-  unsigned w = blockIdx.x;
-  if ((total & 7u) == 0u) w = (w & 7u) * (total >> 3) + (w >> 3);
-  const int b = (int)(w / (unsigned)(tm * tn));
-  const int trem = (int)(w % (unsigned)(tm * tn));
-  const int m0 = (trem / tn) * TM, n0 = (trem % tn) * TM;
-
-  // loader role: threads 0..127 stream one descriptor of image 1 each (64 contiguous bytes per chunk), 128..255 image 2
-  const int img = tid >> 7, lr = tid & 127;
-  const int grow = (img ? n0 : m0) + lr;
-  const bool rvalid = grow < (img ? N2 : N1);
-  const float* src = (img ? desc2 + (size_t)b * N2 * D : desc1 + (size_t)b * N1 * D) + (size_t)(rvalid ? grow : 0) * D;
-  float4 pre[TK / 4];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < TK / 4; ++q)
-      pre[q] = rvalid ? reinterpret_cast<const float4*>(src + k0)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto lstore = [&](int buf) {
-    float* dst = &lds[buf][img][0][lr];
-#pragma unroll
-    for (int q = 0; q < TK / 4; ++q) {
-      dst[(4 * q + 0) * TM] = pre[q].x;
-      dst[(4 * q + 1) * TM] = pre[q].y;
-      dst[(4 * q + 2) * TM] = pre[q].z;
-      dst[(4 * q + 3) * TM] = pre[q].w;
-    }
-  };
-
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-  const int h = lane >> 5, jl = lane & 31;
-  gload(0);
-  lstore(0);
-  __syncthreads();
-  const int nk = D / TK;
-  for (int c = 0; c < nk; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nk) gload((c + 1) * TK);
-    const float* Ab = &lds[buf][0][h][wr * 64 + jl];
-    const float* Bb = &lds[buf][1][h][wc * 64 + jl];
-#pragma unroll
-    for (int kk = 0; kk < TK / 2; ++kk) {
-      const float a0 = Ab[2 * kk * TM], a1 = Ab[2 * kk * TM + 32];
-      const float b0 = Bb[2 * kk * TM], b1 = Bb[2 * kk * TM + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if (c + 1 < nk) lstore(buf ^ 1);
-    __syncthreads();
-  }
+  const auto [b, m0, n0, wr, wc, h, jl] = mfma_dot_tile(desc1, desc2, N1, N2, D, lds, acc, [](const float4(&)[TK / 4]) {});
+  const int lane = threadIdx.x & 63;
 
   // ---- epilogue: C/D layout of the 32x32 tile: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) ----------
 #pragma unroll
@@ -199,7 +115,7 @@ nn_match_finish_kernel(const u64* __restrict__ rowkey, const u64* __restrict__ c
                        int* __restrict__ m_idx1, int* __restrict__ m_idx2, float* __restrict__ score,
                        int* __restrict__ count) {
   __shared__ int wsum[16];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   int base = 0;
   for (int i0 = 0; i0 < N1; i0 += 1024) {  // one pass for up to 1024 keypoints: a single memory latency per pair
     const int i = i0 + tid;
@@ -215,24 +131,12 @@ nn_match_finish_kernel(const u64* __restrict__ rowkey, const u64* __restrict__ c
         keep = (d < nn_thresh) && ((unsigned)colkey[(size_t)b * N2 + j] == (unsigned)i);
       }
     }
-    const u64 bal = __ballot(keep);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull)), total = __popcll(bal);
-    if (lane == 0) wsum[wave] = total;
-    __syncthreads();
-    int off = base, all = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      if (w < wave) off += wsum[w];
-      all += wsum[w];
-    }
+    const size_t p = (size_t)b * N1 + compact_slot<16>(keep, wsum, base);
     if (keep) {
-      const size_t p = (size_t)b * N1 + off + before;
       m_idx1[p] = i;
       m_idx2[p] = (int)j;
       score[p] = d;
     }
-    base += all;
-    __syncthreads();
   }
   if (tid == 0) count[b] = base;
 }
@@ -312,15 +216,12 @@ extern "C" int dfepe_nn_match_two_way(const float* desc1, const float* desc2, in
     return (hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st) == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;
   }
   if (!desc1 || !desc2 || !workspace || !m_idx1 || !m_idx2 || !score) return DFEPE_ERR_INVALID_ARG;
-  if (D % 32 != 0) return DFEPE_ERR_UNSUPPORTED;  // K is consumed in 16-float chunks, two per 128-byte line (SuperPoint: D = 256)
-  if (((uintptr_t)desc1 | (uintptr_t)desc2) & 15u) return DFEPE_ERR_INVALID_ARG;
-  if (((uintptr_t)workspace) & 7u) return DFEPE_ERR_INVALID_ARG;
+  unsigned tiles;
+  if (const int rc = match_tile_plan(desc1, desc2, workspace, B, N1, N2, D, &tiles)) return rc;
   u64* rowkey = static_cast<u64*>(workspace);
   u64* colkey = rowkey + (size_t)B * N1;
   if (hipMemsetAsync(workspace, 0xff, dfepe_nn_match_workspace_bytes(B, N1, N2), st) != hipSuccess) return DFEPE_ERR_HIP;
-  const size_t tiles = (size_t)((N2 + TM - 1) / TM) * ((N1 + TM - 1) / TM) * B;
-  if (tiles > 0x7fffffffu) return DFEPE_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(nn_match_tile_kernel, dim3((unsigned)tiles), dim3(256), 0, st, desc1, desc2, N1, N2, D, rowkey, colkey);
+  hipLaunchKernelGGL(nn_match_tile_kernel, dim3(tiles), dim3(256), 0, st, desc1, desc2, N1, N2, D, rowkey, colkey);
   hipLaunchKernelGGL(nn_match_finish_kernel, dim3(B), dim3(1024), 0, st, rowkey, colkey, N1, N2, nn_thresh, m_idx1, m_idx2,
                      score, count);
   return (hipGetLastError() == hipSuccess) ? DFEPE_OK : DFEPE_ERR_HIP;

@@ -91,25 +91,6 @@ __global__ void __launch_bounds__(kThreads) sp_nms_wide_round_kernel(const float
   if (s != sp::kUndecided) state[i] = s;
 }
 
-// Position of each lane's kept item in the compact row-major list (ballot prefix per wave, wave totals in LDS); every lane of
-// the workgroup calls it.  base: items before this trip, advanced by the trip's total.
-__device__ inline int compact_slot(bool keep, int* wsum, int& base) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long bal = __ballot(keep);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull)), total = __popcll(bal);
-  __syncthreads();  // wsum of the trip before has been read
-  if (lane == 0) wsum[wave] = total;
-  __syncthreads();
-  int off = base, all = 0;
-#pragma unroll
-  for (int w = 0; w < kNmsThreads / WAVE; ++w) {
-    if (w < wave) off += wsum[w];
-    all += wsum[w];
-  }
-  base += all;
-  return off + before;
-}
-
 template <bool LDS>
 __global__ void __launch_bounds__(kNmsThreads) sp_nms_kernel(const float* __restrict__ heatmap, int H, int W, float conf_thresh, int d,
                                                              int r, unsigned char* ws_state, int* ws_list, int cap,
@@ -137,7 +118,7 @@ __global__ void __launch_bounds__(kNmsThreads) sp_nms_kernel(const float* __rest
     for (int i0 = 0; i0 < n; i0 += kNmsThreads) {
       const int i = i0 + tid;
       const bool open = i < n && state[i] == sp::kUndecided;
-      const int k = compact_slot(open, wsum, n_work);
+      const int k = compact_slot<kNmsThreads / WAVE>(open, wsum, n_work);
       if (open) list[k] = i;
     }
   }
@@ -170,7 +151,7 @@ __global__ void __launch_bounds__(kNmsThreads) sp_nms_kernel(const float* __rest
       keep = state[i] == sp::kKept && sp::inside_border(y, x, H, W, r);
       nms_map[(size_t)b * n + i] = keep ? 1.0f : 0.0f;
     }
-    const int k = compact_slot(keep, wsum, base);
+    const int k = compact_slot<kNmsThreads / WAVE>(keep, wsum, base);
     if (keep && k < cap) {  // k < cap always (two kept points never share a (d+1) x (d+1) block); the test keeps a wrong cap harmless
       const size_t p = (size_t)b * cap + k;
       pts[2 * p] = x;
