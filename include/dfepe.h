@@ -1548,6 +1548,74 @@ int dfepe_sample_sets(void *stream, int B, int N, int H, int S, unsigned long lo
                       const float *weights, const int *n_valid, int *idx, int *fallback, void *workspace);
 int dfepe_sampler_advance(void *stream, unsigned *counter, unsigned by);
 
+/*
+ * The sample-loss branch (csrc/sample_loss.hip, csrc/sample_loss_math.h).
+ * Replaces: Fit.forward of deepFEPE/models/DeepFNetSampleLoss.py:364-436 around its fits (np.random.choice(n, topK, p=p) 100 times per
+ *           pair, torch.topk of get_unique, the three torch.gather, prod(1000 w) / (sum + 1e-10)) and loss_selected_F of
+ *           deepFEPE/train_good_utils.py:387-426.  The fits themselves are dfepe_w8pt_fwd_shared / dfepe_w8pt_bwd on B H problems of K.
+ * Notation: B pairs, N correspondences, H sets per pair (selects_each_sample = 100), K draws per set (topK = 20), M virtual points.
+ * No kernel uses atomics, allocates or synchronises with the host; every sum has a fixed order (two runs agree bit for bit); each
+ * entry is one launch (two for a weighted draw) on `stream`: a linear chain, capturable.  Floats are computed in fp64 and rounded
+ * once.  dfepe_version() stays 154 with this addition: nothing that existed changes.
+ *
+ * dfepe_sample_multisets: idx [B,H,K] int32 drawn WITH replacement in proportion to weights [B,N] over the first
+ *   n = clamp(n_valid[b], K, N) correspondences.  seed, offset, counter, the streams, n_valid, the quantisation q, the prefix sums
+ *   P[0 .. n] and the workspace (dfepe_sample_sets_workspace_bytes(B, N, 1) bytes, 16-byte aligned) are those of dfepe_sample_sets
+ *   with K in the place of S.  Draw j of set h of pair b: t = mulhi64(r64_j, P[n]); the index is the largest i < n with P[i] <= t
+ *   (binary search).  One lane per set, exactly 2 K words (K odd: the last block's upper half is not used), no rejection loop.  A
+ *   weight that is NaN, +-inf, <= 0 or below 2^-30 of the pair's largest (q = 0) is never drawn.  The bias of a draw is at most
+ *   P[n] / 2^64 < N 2^-34.  A pair without any q > 0 is drawn uniformly with replacement, index = mulhi64(r64_j, n), and
+ *   fallback[b] = 1 (fallback [B] int32 or NULL).  weights NULL: every pair is drawn that way, no workspace, fallback = 0.
+ *   A set depends on (seed, off, b, h, n, K) and its pair's weights only.  dfepe_sampler_advance serves the counter.
+ *   Refusals, on the host before any HIP call, in this order: B or N < 0, H < 1, K outside 8..32, N < K: INVALID_ARG.  B == 0
+ *   returns OK.  A NULL idx: INVALID_ARG.  Weights with a NULL or misaligned workspace: INVALID_ARG.  B H K > 2^31 - 1:
+ *   UNSUPPORTED.  Weights with N > 2^20: UNSUPPORTED.
+ *
+ * dfepe_topk_select: idx [B,K] int32 and, unless NULL, values [B,K]: the K largest of x[b, :n], n = clamp(n_valid[b], K, N) (n_valid
+ *   NULL = N), in descending order.  The rule: values compare as floats (a denormal is its value, -0 = +0); equal values go lowest
+ *   index first; NaN is greater than everything, as torch.topk orders it, lowest index first among NaNs.  One wavefront per pair,
+ *   K rounds over the n values.
+ *   Refusals in order: B < 0, N < 1, K < 1, K > N: INVALID_ARG.  B == 0: OK.  A NULL x or idx: INVALID_ARG.  B K > 2^31 - 1: UNSUPPORTED.
+ *
+ * dfepe_sample_gather: pts1, pts2 [B,N,3], weights [B,N], idx [B,H,K] -> pts1_sel, pts2_sel [B H,K,3], w_sel [B H,K] (exact copies, the
+ *   layout the fit entry takes) and, unless NULL, accu [B,H] = prod_k (1000 w[idx_k]) / (sum over the pair's H products + 1e-10)
+ *   (DeepFNetSampleLoss.py:418-419).  Product and sum are fp64, the quotient is rounded once.  This differs from the reference's
+ *   float32 where its product overflows or underflows (float32 gives inf / NaN or 0 / 0-sum there; fp64 keeps 20 factors of 1e-12).
+ *   An index outside [0, N) is the caller's error; it is clamped into range, never dereferenced.
+ *   Refusals in order: B < 0, N, H or K < 1: INVALID_ARG.  B == 0: OK.  A NULL pointer other than accu: INVALID_ARG.
+ *   B H K > 2^31 - 1: UNSUPPORTED.
+ *
+ * dfepe_sample_floss_fwd / _bwd: F_sel [B,H,9], T1, T2 [B,9] (t_stride = 9) or one [9] (t_stride = 0), virt1, virt2 [B,M,3].
+ *   loss_sum [B,H] = sum over the M virtual points of compute_epi_residual(T1 virt1, T2 virt2, F_sel[b,h], clamp_at)
+ *   (utils_F.py:400-413); T v is formed in fp64 and rounded to float as dfepe_floss_fwd does, the residual and its sum are fp64.
+ *   Backward: g_loss_sum [B,H] -> g_F [B,H,9] (written); the gradient passes where the residual <= clamp_at.  One workgroup per pair:
+ *   the pair's virtual points are read and transformed once, into LDS; one wavefront per set.  (dfepe_floss_fwd takes 16 layers.)
+ *   Refusals in order: B < 0, H < 1, M < 1, t_stride not 0 or 9: INVALID_ARG.  B == 0: OK.  A NULL pointer: INVALID_ARG.
+ *   M > dfepe_sample_loss_max_virt() (2048: 24 bytes of LDS per point) or B H > 2^31 - 1: UNSUPPORTED.
+ *
+ * dfepe_sample_scatter_bwd: g_w [B,N] (written) = for every correspondence the sum over the cells (h, k) of its pair that name it of
+ *   g_w_sel[b,h,k] (NULL = 0) and, when g_accu [B,H] is given, of the adjoint of accu: accu[b,h] (g_accu[b,h] - G) / w, G = sum_h
+ *   g_accu accu.  Repeats within a set and across sets all count; a correspondence never drawn gets exact 0.  One lane per
+ *   correspondence walks the H K cells in order and sums in fp64; the cells are staged in LDS dfepe_sample_scatter_chunk() at a
+ *   time, so H K has no limit.  Where w = 0 exactly the accu term is taken as 0 (torch differentiates the product through the other
+ *   factors there; a weighted draw never returns such a correspondence).
+ *   Refusals in order: B < 0, N, H or K < 1: INVALID_ARG.  B == 0: OK.  A NULL idx or g_w: INVALID_ARG.  g_accu with a NULL weights or
+ *   accu: INVALID_ARG.  B H K > 2^31 - 1 or B > 65535: UNSUPPORTED.
+ */
+int dfepe_sample_loss_max_virt(void);
+int dfepe_sample_scatter_chunk(void);
+int dfepe_sample_multisets(void *stream, int B, int N, int H, int K, unsigned long long seed, unsigned offset, const unsigned *counter,
+                           const float *weights, const int *n_valid, int *idx, int *fallback, void *workspace);
+int dfepe_topk_select(void *stream, const float *x, const int *n_valid, int B, int N, int K, int *idx, float *values);
+int dfepe_sample_gather(void *stream, const float *pts1, const float *pts2, const float *weights, const int *idx, int B, int N, int H,
+                        int K, float *pts1_sel, float *pts2_sel, float *w_sel, float *accu);
+int dfepe_sample_floss_fwd(void *stream, const float *F_sel, int B, int H, const float *T1, const float *T2, int t_stride,
+                           const float *virt1, const float *virt2, int M, float clamp_at, float *loss_sum);
+int dfepe_sample_floss_bwd(void *stream, const float *F_sel, int B, int H, const float *T1, const float *T2, int t_stride,
+                           const float *virt1, const float *virt2, int M, float clamp_at, const float *g_loss_sum, float *g_F);
+int dfepe_sample_scatter_bwd(void *stream, const float *g_w_sel, const float *g_accu, const float *weights, const float *accu,
+                             const int *idx, int B, int N, int H, int K, float *g_w);
+
 #ifdef __cplusplus
 }
 #endif

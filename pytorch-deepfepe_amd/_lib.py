@@ -46,6 +46,7 @@ SP_LDS_PIXELS = 12288  # dfepe_sp_nms: pixels per image up to which no workspace
 SP_MAX_PATCH = 63  # dfepe_sp_soft_argmax: largest patch_size (sp::kMaxPatch)
 DSAC_MIN_SAMPLE, DSAC_MAX_SAMPLE = 8, 16  # dfepe_dsac: correspondences per hypothesis (ds::kMinSample, ds::kMaxSample)
 SAMPLER_MAX_WEIGHTED_N = 1 << 20  # dfepe_sample_sets: correspondences per pair in weighted mode (sm::kMaxWeightedN)
+SAMPLE_MIN_DRAWS, SAMPLE_MAX_DRAWS = 8, 32  # dfepe_sample_multisets: draws per set (sl::kMinDraws, sl::kMaxDraws)
 INLIER_TABLE_MAX_THDS = 16  # dfepe_inlier_table: inlier thresholds per call, and mask thresholds per call (ce::kMaxThds)
 
 _P = c_void_p
@@ -181,6 +182,14 @@ _SIGNATURES = {
     "dfepe_sample_sets_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dfepe_sample_sets": (c_int, [_P, c_int, c_int, c_int, c_int, c_ulonglong, c_uint, _P, _P, _P, _P, _P, _P]),
     "dfepe_sampler_advance": (c_int, [_P, _P, c_uint]),
+    "dfepe_sample_loss_max_virt": (c_int, []),
+    "dfepe_sample_scatter_chunk": (c_int, []),
+    "dfepe_sample_multisets": (c_int, [_P, c_int, c_int, c_int, c_int, c_ulonglong, c_uint, _P, _P, _P, _P, _P, _P]),
+    "dfepe_topk_select": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "dfepe_sample_gather": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "dfepe_sample_floss_fwd": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_float, _P]),
+    "dfepe_sample_floss_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_float, _P, _P]),
+    "dfepe_sample_scatter_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -3,6 +3,8 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
     reference module                         this package
     deepFEPE.models.DeepFNet            ->   compat.DeepFNet        (NormalizeAndExpand_HW, Fit, DeepFNet)
+    deepFEPE.models.DeepFNetSampleLoss  ->   compat.DeepFNetSampleLoss (Fit with the top-K and sampled-set fits, Norm8PointNet: the
+                                                                    if_sample_loss model; sets drawn on the stream or by NumPy)
     deepFEPE.models.ErrorEstimators     ->   compat.ErrorEstimators (stock PyTorch; not part of the hot path)
     deepFEPE.dsac_tools.utils_F         ->   compat.utils_F
     deepFEPE.dsac_tools.utils_geo       ->   compat.utils_geo
@@ -36,7 +38,7 @@ argument order, defaults, return arity, tensor layouts and dict keys, backed by 
 
 See INTEGRATION.md for how train_good.py is pointed at these.
 """
-from . import DeepFNet, ErrorEstimators, H_loss, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, evaluation_epiDist, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
+from . import DeepFNet, DeepFNetSampleLoss, ErrorEstimators, H_loss, captured, descriptor_evaluation, detector_evaluation, dsac, eval_tools, evaluate_frontend, evaluation_epiDist, model_wrap, superpoint_process, train_good_utils, utils_F, utils_geo, utils_misc, utils_opencv, utils_vis  # noqa: F401
 from .captured import CapturedStep  # noqa: F401
 from .descriptor_evaluation import compute_homography, compute_homography_batch, get_inliers, get_inliers_cv, homography_estimation, warp_keypoints  # noqa: F401
 from .detector_evaluation import compute_repeatability, compute_repeatability_batch  # noqa: F401

@@ -246,8 +246,8 @@ def get_all_loss_DeepF(outs, pts1_virt_ori, pts2_virt_ori, Ks, loss_params, get_
                  them ready; without it get_Rt_loss launches the pose kernel itself.  Same numbers either way.
       "floss_grad": False -- promise that no gradient will be asked of loss_F / loss_layers (an objective of the pose terms
                  only, the reference's if_qt_loss, Train_model_pipeline.py:580-587): skips the F-loss adjoint work of the launch."""
-    if loss_params.get("if_tri_depth", False) or loss_params.get("if_sample_loss", False):
-        raise NotImplementedError("if_tri_depth / if_sample_loss are outside the built hot path (all shipped configs disable them)")
+    if loss_params.get("if_tri_depth", False):
+        raise NotImplementedError("if_tri_depth is outside the built hot path (all shipped configs disable it)")
     logits_softmax = outs["weights"]
     F_est_normalized, T1, T2 = outs["F_est"], outs["T1"], outs["T2"]
     out_layers, residual_layers, weights_layers = outs["out_layers"], outs["residual_layers"], outs["weights_layers"]
@@ -306,6 +306,16 @@ def get_all_loss_DeepF(outs, pts1_virt_ori, pts2_virt_ori, Ks, loss_params, get_
         "loss_min_layers": row_min,  # per_pair.min(dim=1)[0] (:375); these two carry no gradient here (logged only)
         "loss_min_batch": col_min,   # per_pair.min(dim=0)[0] (:376)
     }
+    if loss_params.get("if_sample_loss", False):
+        # loss_selected_F (:387-426): per layer and pair the mean over [H sets, M virtual points] of compute_epi_residual with the
+        # literal clamp 0.02 (:406), then the mean over pairs, then over layers.  One launch per layer for all pairs and sets; every
+        # pair has the same H and M, so the mean of the per-pair means is the sum over everything divided by B H M.
+        loss_selected_layers = []
+        for F_sel in outs["out_sample_selected_batch_layers"][:depth]:
+            loss_sel = ops.sample_floss(F_sel, T1, T2, pts1_virt_ori, pts2_virt_ori, 0.02)  # [B,H]
+            loss_selected_layers.append(loss_sel.sum() / float(loss_sel.numel() * M))
+        losses_dict.update({"loss_selected_F": sum(loss_selected_layers) / len(loss_selected_layers),
+                            "loss_selected_layers": loss_selected_layers})
     loss_epi_res_all = 0.0
     loss_epi_res_layers = []
     if m_epi is not None:

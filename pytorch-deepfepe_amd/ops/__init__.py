@@ -21,6 +21,7 @@ from .matching import gather_matches, knn_match, nn_match_two_way  # noqa: F401
 from .robust import (_recover_pose_camera, homography_corners, homography_transfer, lmeds_essential, lmeds_essential_pose,  # noqa: F401
                      lmeds_fundamental, lmeds_pose, ransac_essential, ransac_essential_pose, ransac_fundamental, ransac_homography,
                      ransac_in_front, ransac_pose)
+from .sample_loss import sample_fits, sample_floss, sample_gather, sample_multisets, sample_scatter_bwd, topk_select  # noqa: F401
 from .sampler import sample_sets, sampler_advance  # noqa: F401
 from .structure import correct_matches, reproject, triangulate, two_view_structure  # noqa: F401
 from .superpoint import sp_flatten, sp_nms, sp_nms_capacity, sp_sample_desc, sp_soft_argmax  # noqa: F401
